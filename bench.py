@@ -1,12 +1,17 @@
 #!/usr/bin/env python3
 """Benchmark of the batched synthesis hot path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload aac|mp3|vorbis|flac]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload aac|mp3|vorbis|flac] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one pass of the hot path over one batch of synthetic, HBM-resident input.  Default
 workload = BASELINE config 2: AAC-LC 48 kHz stereo, 65 536 long-block frames (128 chains x 1024
 frames, KBD windows), 1024-pt IMDCT + window + overlap-add.  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: set-up, spin-up + W warm-up steps, the K timed steps,
+the outputs (--dump-outputs) and the line.  --full adds everything else the line can carry: the
+cold-start region, the repeats, the oracle check of the timed batch, the copy probes and clocks, the
+other workloads, the host-to-host and decoders lines, the CPU baseline and the N > 1 legs.
 
 Multi-GPU: one process per GPU, chains sharded across ranks with NO data-path collective (streams are
 independent) -- weak scaling: every rank runs the full per-GPU batch.  RCCL is used only
@@ -67,6 +72,7 @@ def make_workload(name, torch, ctx, seed, scale=1.0, mix=0.0, emulate=False):
             delay.reverse()
         step.input = coeffs
         step.aac = (coeffs, side)
+        step.outputs = lambda: {"pcm": pcm, "delay": delay[0]}  # what the last step returned (its delay_out is delay[0] now)
 
         def chunk_step(first, count):  # chains [first, first + count) from a zero state (symaccel_exchange_pipelined's callback)
             dsp.synth(coeffs[first:first + count], side[first:first + count], torch.zeros((count, 1024), device=dev), pcm[first:first + count],
@@ -814,6 +820,38 @@ def verify_vorbis_chains(name, step, torch, sync):
             "seed": VERIFY_SEED, "samples_compared": checked, "mismatches": bad, "criterion": "bit-identical f32 (value comparison)"}
 
 
+DUMP_BUDGET = 64 << 20  # bytes that --dump-outputs writes in all
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET):
+    """--dump-outputs: every array of `arrays` (name -> tensor) as <out_dir>/<name>.npy, float32 (float64 for 64-bit floats and
+    integer data: exact for 32-bit samples).  An array that does not fit its share of `budget` is cut to a fixed sample of rows
+    (first axis): np.sort(np.random.default_rng(0).choice(rows, kept, replace=False)), the same rows in every run.  Returns
+    what was written, for the line."""
+    import torch
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    items = sorted(arrays.items(), key=lambda kv: kv[1].numel())
+    done = {}
+    for i, (name, t) in enumerate(items):
+        dtype = np.float32 if (t.dtype.is_floating_point and t.element_size() <= 4) else np.float64
+        share = budget // (len(items) - i)
+        n = int(t.shape[0]) if t.dim() else 1
+        row_bytes = (t.numel() // max(n, 1)) * np.dtype(dtype).itemsize
+        kept = min(n, share // row_bytes) if row_bytes else n
+        if kept < 1:
+            raise RuntimeError("--dump-outputs: one row of %s (%d bytes) exceeds its share of %d bytes" % (name, row_bytes, share))
+        if kept < n:
+            rows = np.sort(np.random.default_rng(0).choice(n, kept, replace=False))
+            t = t.index_select(0, torch.from_numpy(rows).to(t.device))
+        a = t.detach().cpu().numpy().astype(dtype)
+        np.save(out_dir / (name + ".npy"), a)
+        budget -= a.nbytes
+        done[name] = {"shape": list(arrays[name].shape), "dtype": np.dtype(dtype).name, "rows_kept": kept if kept < n else None}
+    return {"dir": str(out_dir), "arrays": done,
+            "note": "what the last timed step computed; rows_kept = np.sort(np.random.default_rng(0).choice(shape[0], rows_kept, replace=False))"}
+
+
 def workload_input(name, step):
     """The spectra tensor a step consumes (what a one-to-all scatter would have to move)."""
     return step.input
@@ -1239,6 +1277,13 @@ def main():
     ap.add_argument("--no-verify", action="store_true", help="measurement builds whose results are wrong on purpose (SYMACCEL_TUNE_*_ABLATE): skip the oracle check; the line says so")
     ap.add_argument("--verify-seed", type=int, default=None,
                     help="seed of the chains / windows the `verified` blocks sample beside the fixed ones (default: drawn per run, printed in the line)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline (cold start, repeats, oracle check, copy probes, clocks, "
+                         "other workloads, host-to-host, decoders, CPU baseline, N > 1 legs); the --no-* options still apply")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, at most 64 MiB "
+                         "in all: a fixed sample of rows of a larger output); the inputs are seeded, so two builds compare output for "
+                         "output (the in-place FLAC / ALAC workloads also depend on how many steps ran before)")
     args = ap.parse_args()
     global VERIFY_SEED
     VERIFY_SEED = args.verify_seed if args.verify_seed is not None else int.from_bytes(os.urandom(4), "little")
@@ -1363,10 +1408,10 @@ def main():
     step, units, unit_name, alg_bytes, config, kernel, result = make_workload(args.workload, torch, ctx, 1234 + rank, args.scale,
                                                                               args.aac_mix, emulate)
     log("workload built: %s" % config["workload"])
-    # the same W + K twice: from idle (reported as `cold_start`), then at the sustained clocks (the line's `value`)
+    # --full: the same W + K twice, from idle (reported as `cold_start`), then at the sustained clocks (the line's `value`)
     spin = 0.0 if (args.no_spinup or emulate) else args.spinup_ms / 1e3
     cold = None
-    if spin > 0.0:
+    if spin > 0.0 and args.full:
         sync()
         time.sleep(0.25)  # (an idle board: the workload's construction has just run kernels of its own)
         e_c, l_c, _ = timed(step, args.steps, args.warmup)
@@ -1376,10 +1421,14 @@ def main():
         log("cold-start region done: %.3f ms/step" % (e_c / args.steps * 1e3))
     elapsed, launch_s, mine = timed(step, args.steps, args.warmup, spin)
     log("timed region done: %.3f ms/step (device), %.3f ms/step (wall)" % (launch_s * 1e3, elapsed / args.steps * 1e3))
+    dumped = None
+    if args.dump_outputs and rank == 0:  # (before anything below runs the step again or reuses its buffers)
+        dumped = dump_outputs(args.dump_outputs, step.outputs() if hasattr(step, "outputs") else {"output": result})
+        log("outputs written to %s" % args.dump_outputs)
     # the same W + K region again, `--repeats` times back to back: the line's `value` stays the first region (the contract's "exactly
     # K steps"); the repeats say how far one 4 ms region is from the next on this board (`repeats.value_median`, `spread_frac`)
     repeats = None
-    if args.repeats > 0 and not emulate:
+    if args.full and args.repeats > 0 and not emulate:
         per, dev_ms = [elapsed / args.steps * 1e3], [launch_s * 1e3]
         for _ in range(args.repeats):
             e_r, l_r, _ = timed(step, args.steps, args.warmup)
@@ -1395,9 +1444,9 @@ def main():
     verified = None
     if args.no_verify:
         verified = {"skipped": "--no-verify: NOT a measurement of the product (an ablation build's results are wrong on purpose)"}
-    elif rank == 0 and hasattr(step, "verify"):
+    elif args.full and rank == 0 and hasattr(step, "verify"):
         verified = step.verify()
-    if not args.no_verify and rank == 0 and args.workload in ("aac", "mp3", "vorbis", "vorbisf", "vorbisf2"):
+    if args.full and not args.no_verify and rank == 0 and args.workload in ("aac", "mp3", "vorbis", "vorbisf", "vorbisf2"):
         verified = verify_sampled_chains(args.workload, step, torch, sync)  # raises on a mismatch: no line for a wrong result
         log("timed batch verified against the oracle: %d samples" % verified["samples_compared"])
     per_rank_ms = [mine / args.steps * 1e3]
@@ -1415,7 +1464,7 @@ def main():
     # the same batch when it starts and ends on ONE rank -- scatter of the input shards from rank 0, the
     # synthesis step, gather of the PCM shards on rank 0.  Reported beside `value` (which is (i): shards resident per GPU).
     exchange = None
-    if world > 1 and not args.no_exchange and args.workload in ("aac", "mp3", "vorbis"):
+    if args.full and world > 1 and not args.no_exchange and args.workload in ("aac", "mp3", "vorbis"):
         try:  # an optional leg must never cost the headline line (an error here is reported in the line instead)
             src = workload_input(args.workload, step)
             secs = timed_exchange(src, result, step, dist, sync, device=red_dev, reps=2 if emulate else 3)
@@ -1429,7 +1478,7 @@ def main():
     # BASELINE config 4 is the one the north star phrases as an 8-GPU job (64 streams x 8 ch sharded 8 streams per GPU):
     # with N > 1 and another headline workload, add its line (same timing discipline, fewer steps) beside the headline.
     config4 = None
-    if world > 1 and not args.no_config4 and args.workload != "vorbis":
+    if args.full and world > 1 and not args.no_config4 and args.workload != "vorbis":
         try:
             st4, units4, unit4, bytes4, cfg4, kernel4, _ = make_workload("vorbis", torch, ctx, 4321 + rank, args.scale, 0.0, emulate)
             e4, l4, _ = timed(st4, max(2, args.steps // 2), 1 if emulate else 2, spin)
@@ -1442,17 +1491,17 @@ def main():
     # The same run's copy ceilings and the other BASELINE configs under the same clock: optional legs, each in
     # its own try so that nothing here can cost the headline line.
     ceiling = None
-    if world == 1 and not emulate and not args.no_copy_ceiling:
+    if args.full and world == 1 and not emulate and not args.no_copy_ceiling:
         try:
             ceiling = copy_ceiling(ctx, torch, 64)
         except Exception as e:  # noqa: BLE001
             ceiling = {"error": "%s: %s" % (type(e).__name__, e)}
         log("copy probes done")
     clocks = None
-    if world == 1 and not emulate and not args.no_copy_ceiling:
+    if args.full and world == 1 and not emulate and not args.no_copy_ceiling:
         clocks = sample_clocks(step, sync)
     others = None
-    if world == 1 and args.workload == "aac" and not args.no_others:
+    if args.full and world == 1 and args.workload == "aac" and not args.no_others:
         others = {}
         # (key, workload, block-switch probability): the BASELINE configs at their headline settings, then what a REAL stream
         # costs -- AAC with legal window-sequence walks (5 % / 25 % of the long frames start a LONG_START -> EIGHT_SHORT.. ->
@@ -1488,7 +1537,7 @@ def main():
     # page-locked host memory (per-GPU producers: no rank-0 bottleneck) --, (b) the exchange leg once more through the C ABI.
     # Both last, (b) on a watchdog: nothing here can cost what was measured above.
     producers, exchange_c, hung = None, None, False
-    if world > 1 and not emulate and not one_gpu_smoke and args.workload == "aac" and not args.no_host_path:
+    if args.full and world > 1 and not emulate and not one_gpu_smoke and args.workload == "aac" and not args.no_host_path:
         try:
             h2h = host_to_host_aac(sa, ctx, torch, result, step.input, units)
             worst = max_over_ranks(h2h["ms"] / 1e3, dist, device=red_dev)
@@ -1496,7 +1545,7 @@ def main():
                          "ms": worst * 1e3, "value": units * world / worst, "unit": unit_name + "/s", "GBps_each_way_per_rank": h2h["GBps_each_way"]}
         except Exception as e:  # noqa: BLE001
             producers = {"error": "%s: %s" % (type(e).__name__, e)}
-    if world > 1 and not host_collectives and not args.no_exchange and args.workload in ("aac", "mp3", "vorbis"):
+    if args.full and world > 1 and not host_collectives and not args.no_exchange and args.workload in ("aac", "mp3", "vorbis"):
         exchange_c, hung = guarded(lambda: exchange_c_api(ctx, torch, dist, world, rank, workload_input(args.workload, step), result, step, units,
                                                           unit_name, sync), 150)
 
@@ -1512,8 +1561,10 @@ def main():
             "warmup": args.warmup,
             "ms_per_step": elapsed / args.steps * 1e3,
             "schema": 5,
-            "protocol": ("sustained (spinup %d ms of back-to-back steps, then W warm-up + K timed steps); `cold_start` = the same W + K "
-                         "from an idle board, the protocol of BENCH_r01 / r02" % args.spinup_ms) if spin > 0.0 else "cold (W + K from an idle board)",
+            "protocol": ("sustained (spinup %d ms of back-to-back steps, then W warm-up + K timed steps)" % args.spinup_ms
+                         + ("; `cold_start` = the same W + K from an idle board, the protocol of BENCH_r01 / r02" if cold else ""))
+                        if spin > 0.0 else "cold (W + K from an idle board)",
+            "full": args.full,
             "spinup_ms": (args.spinup_ms if spin > 0.0 else 0),
             "cold_start": cold,
             "repeats": repeats,
@@ -1562,6 +1613,8 @@ def main():
                                                     "wavefront walk's pattern); frames_per_workgroup_walk_256 = the four wavefronts of a "
                                                     "workgroup share 256 consecutive frames round-robin, 16 KiB contiguous per step (the "
                                                     "headline kernel's pattern: `frac_of_same_pattern_copy`); `peak` stays the HBM3E spec")
+        if dumped:
+            out["outputs"] = dumped
         if others:
             out["other_workloads"] = others
         if args.workload in ("alac", "alacp"):
@@ -1579,7 +1632,7 @@ def main():
             out["per_gpu_producers"] = producers
         if exchange_c:
             out["exchange_c_api"] = exchange_c
-        if world == 1 and args.workload == "aac" and not args.no_host_path and not emulate:
+        if args.full and world == 1 and args.workload == "aac" and not args.no_host_path and not emulate:
             out["host_to_host"] = host_to_host_aac(sa, ctx, torch, result, step.input, units)
             try:  # BASELINE config 3 the same way: f32 spectra against the entropy decoder's int16 samples (half the bytes in)
                 out["host_to_host_mp3"] = host_to_host_mp3(sa, ctx, torch, 128, 2048, 131072)
@@ -1589,12 +1642,12 @@ def main():
                 out["decoders"] = decoders_workload(quick=True, lookahead=256)  # (the Rust shim's DEFAULT_LOOKAHEAD)
             except Exception as e:  # noqa: BLE001
                 out["decoders"] = {"error": "%s: %s" % (type(e).__name__, e)}
-        if world == 1 and args.workload == "mp3" and not args.no_host_path and not emulate:
+        if args.full and world == 1 and args.workload == "mp3" and not args.no_host_path and not emulate:
             try:
                 out["host_to_host"] = host_to_host_mp3(sa, ctx, torch, int(step.input.shape[0]), int(step.input.shape[1]), units)
             except Exception as e:  # noqa: BLE001
                 out["host_to_host"] = {"error": "%s: %s" % (type(e).__name__, e)}
-        if world == 1 and not args.no_cpu_baseline and not emulate:
+        if args.full and world == 1 and not args.no_cpu_baseline and not emulate:
             # (the int16 MP3 lines are timed against the same CPU restatement as config 3: its synthesis tail; the CPU side of
             # requantize + stereo is a few per cent of that)
             out["cpu_baseline"] = cpu_baseline({"mp3q": "mp3", "mp3q2": "mp3", "vorbisf": "vorbis", "vorbisf2": "vorbis", "aacjs": "aac", "aacjs2": "aac", "aactns": "aac", "flacp": "flac", "alacp": "alac"}.get(args.workload, args.workload))

@@ -134,7 +134,7 @@ def test_bench_gpus_2_starts_two_ranks_by_itself():
     report a two-rank line.  Runs the real control flow -- self-launch under torch.distributed.run on 127.0.0.1, rank /
     device checks, barrier + max-over-ranks clock, scatter -> step -> gather leg, config-4 line -- on CPU tensors through
     the emulation build with gloo (--emulate, test only)."""
-    r, d = _bench(["--gpus", "2", "--emulate", "--steps", "2", "--warmup", "1"])
+    r, d = _bench(["--gpus", "2", "--emulate", "--full", "--steps", "2", "--warmup", "1"])
     assert r.returncode == 0 and d is not None, r.stderr[-3000:]
     assert d["n_gpus"] == 2 and d["steps"] == 2 and d["scaling"] == "weak"
     assert d["ranks"]["world_size"] == 2 and d["ranks"]["backend"] == "gloo"
@@ -158,9 +158,9 @@ def test_bench_refuses_a_launcher_with_the_wrong_world_size():
 
 
 def test_bench_line_carries_the_other_workloads():
-    """The default N = 1 line reports BASELINE configs 3, 4 (one GPU's shard), 5 and the ALAC predictor beside the headline
+    """The --full N = 1 line reports BASELINE configs 3, 4 (one GPU's shard), 5 and the ALAC predictor beside the headline
     (`other_workloads`, 20 / 8 steps each, each in its own try): control flow through the emulation build at a tiny scale."""
-    r, d = _bench(["--emulate", "--scale", "0.0001", "--steps", "2", "--warmup", "1"], timeout=600)
+    r, d = _bench(["--emulate", "--full", "--scale", "0.0001", "--steps", "2", "--warmup", "1"], timeout=600)
     assert r.returncode == 0 and d is not None, r.stderr[-3000:]
     ow = d["other_workloads"]
     assert set(ow) == {"mp3", "vorbis", "flac", "alac", "flac_padded_rows", "alac_padded_rows", "aac_mix_0.05", "aac_mix_0.25", "mp3_mix_0.06", "mp3_int16_one_kernel", "mp3_int16_two_kernels",
@@ -177,3 +177,39 @@ def test_bench_line_carries_the_other_workloads():
     assert d["verified"]["mismatches"] == 0 and d["schema"] == 5 and "protocol" in d and (d.get("repeats") is None or d["repeats"]["regions"] >= 5)
     assert ow["flac"]["kernel"] == "flac_restore_f64_kernel" and ow["mp3"]["kernel"] == "mp3_synth_kernel"
     assert "rows 4608 words apart" in ow["flac_padded_rows"]["workload"] and "rows 4608 words apart" in ow["alac_padded_rows"]["workload"]
+
+
+def test_bench_plain_line_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """Without --full the line carries the headline alone (no second region, no oracle check, no other workloads, no CPU
+    baseline); --dump-outputs writes what the last timed step returned, the same bits in two runs of the same arguments."""
+    lines = []
+    for run in ("a", "b"):
+        r, d = _bench(["--emulate", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / run)], timeout=300)
+        assert r.returncode == 0 and d is not None, r.stderr[-3000:]
+        lines.append(d)
+    d = lines[0]
+    assert d["steps"] == 3 and d["full"] is False and d["ms_per_step"] > 0 and d["unit"] == "frames/s" and d["dtype"] == "f32"
+    assert d["cold_start"] is None and d["repeats"] is None and d["verified"] is None
+    assert not {"other_workloads", "cpu_baseline", "host_to_host", "decoders", "exchange", "config4_vorbis"} & set(d)
+    assert set(d["outputs"]["arrays"]) == {"pcm", "delay"}
+    for name in ("pcm", "delay"):
+        a, b = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))
+        assert a.dtype == np.float32 and list(a.shape) == d["outputs"]["arrays"][name]["shape"]
+        assert np.isfinite(a).all() and np.array_equal(a, b)
+    assert np.load(tmp_path / "a" / "pcm.npy").shape[1:] == (6, 1024)
+
+
+def test_dump_outputs_keeps_a_fixed_sample_of_rows_within_the_budget(tmp_path):
+    import torch
+    sys.path.insert(0, str(ROOT))
+    import bench
+    big = torch.arange(64 * 256, dtype=torch.float32).reshape(64, 256)
+    small = torch.arange(10, dtype=torch.int32)
+    got = bench.dump_outputs(tmp_path, {"big": big, "small": small}, budget=16 * 1024)
+    s = np.load(tmp_path / "small.npy")
+    assert s.dtype == np.float64 and np.array_equal(s, np.arange(10))  # integer data: float64, whole
+    b = np.load(tmp_path / "big.npy")
+    kept = got["arrays"]["big"]["rows_kept"]
+    assert b.dtype == np.float32 and b.shape == (kept, 256) and 0 < kept < 64 and s.nbytes + b.nbytes <= 16 * 1024
+    rows = np.sort(np.random.default_rng(0).choice(64, kept, replace=False))
+    assert np.array_equal(b, big.numpy()[rows])

@@ -4,10 +4,10 @@ OUT=$PWD/gpurun_out; mkdir -p $OUT; export TMPDIR=/tmp
 rocminfo | grep -m3 -i "gfx\|Marketing" > $OUT/rocminfo_r2.txt 2>&1
 timeout 900 python -m pytest tests -m gpu -q -x --timeout 300 2>&1 | tail -15 | tee $OUT/pytest_gpu_r2a.log
 for w in aac mp3 vorbis alac; do
-  timeout 300 python bench.py --workload $w --steps 20 --warmup 3 --no-cpu-baseline > $OUT/r2a_bench_$w.json 2> $OUT/r2a_bench_$w.err
+  timeout 300 python bench.py --full --workload $w --steps 20 --warmup 3 --no-cpu-baseline > $OUT/r2a_bench_$w.json 2> $OUT/r2a_bench_$w.err
   echo "bench $w rc=$?"; tail -n 1 $OUT/r2a_bench_$w.json | cut -c1-260
 done
-timeout 600 python bench.py --workload flac --steps 10 --warmup 2 --no-cpu-baseline > $OUT/r2a_bench_flac.json 2> $OUT/r2a_bench_flac.err
+timeout 600 python bench.py --full --workload flac --steps 10 --warmup 2 --no-cpu-baseline > $OUT/r2a_bench_flac.json 2> $OUT/r2a_bench_flac.err
 echo "bench flac rc=$?"; tail -n 1 $OUT/r2a_bench_flac.json | cut -c1-260; tail -3 $OUT/r2a_bench_flac.err
 ab() {  # workload, libs...
   W=$1; shift

@@ -3,7 +3,7 @@
 OUT=$PWD/gpurun_out; mkdir -p $OUT; export TMPDIR=/tmp; REPO=$PWD
 timeout 900 python -m pytest tests -m gpu -q -x --timeout 300 -k "flac or Flac or FLAC" 2>&1 | grep -v -E "^(RCCL|HIP|ROCm|Hostname|Librccl)" | tail -n 8 > $OUT/r05e_gputest_flac.log
 cat $OUT/r05e_gputest_flac.log
-timeout 600 python bench.py --workload flac --no-others > $OUT/r05e_bench_flac.json 2> $OUT/r05e_bench_flac.err
+timeout 600 python bench.py --full --workload flac --no-others > $OUT/r05e_bench_flac.json 2> $OUT/r05e_bench_flac.err
 echo "flac bench rc=$?"; python - <<'PY'
 import json
 d=json.loads(open("gpurun_out/r05e_bench_flac.json").read().strip().splitlines()[-1])

@@ -13,7 +13,7 @@ for r in d["sweep"]:
 for k in ("mp3_int16_S256","mp3_f32_S256","vorbis_8ch_S64"): print(k, d.get(k,{}).get("packets_per_s"), d.get(k,{}).get("GBps_each_way"))
 PY
 for T in 1 4 16; do $REPO/symphonia_amd/build/decoders_bench --codec aac --streams 256 --lookahead 64 --packets 256 --threads $T; done 2>&1 | cut -c1-330
-timeout 600 python bench.py --workload flac --no-others --no-cpu-baseline --no-copy-ceiling > $OUT/r05f_bench_flac.json 2> $OUT/r05f_bench_flac.err
+timeout 600 python bench.py --full --workload flac --no-others --no-cpu-baseline --no-copy-ceiling > $OUT/r05f_bench_flac.json 2> $OUT/r05f_bench_flac.err
 python - <<'PY'
 import json
 d=json.loads(open("gpurun_out/r05f_bench_flac.json").read().strip().splitlines()[-1])

@@ -5,7 +5,7 @@ timeout 900 python -m pytest tests -m gpu -q -x --timeout 300 2>&1 | grep -v -E 
 cat $OUT/r05h_gputest.log
 for rep in 1 2; do
 for w in "vorbis" "aac --aac-mix 0.25" "aac"; do
-  timeout 300 python bench.py --workload $w --no-others --no-cpu-baseline --no-copy-ceiling --no-host-path --repeats 3 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$w', round(d['ms_per_step'],4), round(d['roofline']['frac'],4), d['repeats']['ms_per_step_median'])"
+  timeout 300 python bench.py --full --workload $w --no-others --no-cpu-baseline --no-copy-ceiling --no-host-path --repeats 3 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$w', round(d['ms_per_step'],4), round(d['roofline']['frac'],4), d['repeats']['ms_per_step_median'])"
 done
 done | tee $OUT/r05h_t1m.txt
 bash tools/gpu_pmc.sh r05h vorbis

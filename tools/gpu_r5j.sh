@@ -1,6 +1,6 @@
 #!/bin/bash
 OUT=$PWD/gpurun_out; mkdir -p $OUT
-timeout 900 python bench.py > $OUT/r05j_default_bench.json 2> $OUT/r05j_default_bench.err; echo rc=$?
+timeout 900 python bench.py --full > $OUT/r05j_default_bench.json 2> $OUT/r05j_default_bench.err; echo rc=$?
 python - <<'PY'
 import json
 d=json.load(open("gpurun_out/r05j_default_bench.json"))

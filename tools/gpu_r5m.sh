@@ -4,7 +4,7 @@ OUT=$PWD/gpurun_out; mkdir -p $OUT; export TMPDIR=/tmp
 timeout 300 python tools/probe_layout.py > $OUT/r05m_probe_layout.json 2> $OUT/r05m_probe_layout.err; echo "probe rc=$?"
 cat $OUT/r05m_probe_layout.json | cut -c1-3000
 for seg in 0 256 260 264 272 288 320 128 132; do
-  timeout 200 python bench.py --segment $seg --no-others --no-cpu-baseline --no-host-path --no-copy-ceiling --repeats 3 > $OUT/r05m_aac_seg$seg.json 2> $OUT/r05m_aac_seg$seg.err
+  timeout 200 python bench.py --full --segment $seg --no-others --no-cpu-baseline --no-host-path --no-copy-ceiling --repeats 3 > $OUT/r05m_aac_seg$seg.json 2> $OUT/r05m_aac_seg$seg.err
   python - $OUT/r05m_aac_seg$seg.json $seg <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

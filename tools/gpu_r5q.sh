@@ -3,7 +3,7 @@
 OUT=$PWD/gpurun_out; mkdir -p $OUT; export TMPDIR=/tmp
 timeout 600 python -m pytest tests/test_alac.py tests/test_alac_packets.py tests/test_gpu_parity.py tests/test_rust_adapters.py tests/test_product_vs_reference_text.py -m gpu -x -q -k "alac or Alac or flac_alac" 2>&1 | tail -3
 for i in 1 2; do
-timeout 300 python bench.py --workload alac --no-cpu-baseline --no-copy-ceiling --repeats 3 2> $OUT/r05q_alac.err > $OUT/r05q_bench_alac_$i.json
+timeout 300 python bench.py --full --workload alac --no-cpu-baseline --no-copy-ceiling --repeats 3 2> $OUT/r05q_alac.err > $OUT/r05q_bench_alac_$i.json
 python - $OUT/r05q_bench_alac_$i.json <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

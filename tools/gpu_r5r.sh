@@ -3,7 +3,7 @@
 OUT=$PWD/gpurun_out; mkdir -p $OUT; export TMPDIR=/tmp
 for w in mp3 mp3q; do
 for seg in 0 64 43 32 22 16 11; do
-  timeout 200 python bench.py --workload $w --segment $seg --no-others --no-cpu-baseline --no-host-path --no-copy-ceiling --repeats 3 2> $OUT/r05r.err > $OUT/r05r_${w}_seg$seg.json
+  timeout 200 python bench.py --full --workload $w --segment $seg --no-others --no-cpu-baseline --no-host-path --no-copy-ceiling --repeats 3 2> $OUT/r05r.err > $OUT/r05r_${w}_seg$seg.json
   python - $OUT/r05r_${w}_seg$seg.json $w $seg <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -3,7 +3,7 @@
 OUT=$PWD/gpurun_out; mkdir -p $OUT; export TMPDIR=/tmp
 for w in vorbis vorbisf; do
 for seg in 0 128 86 100 64 43; do
-  timeout 200 python bench.py --workload $w --segment $seg --no-others --no-cpu-baseline --no-host-path --no-copy-ceiling --repeats 3 2> $OUT/r05s.err > $OUT/r05s_${w}_seg$seg.json
+  timeout 200 python bench.py --full --workload $w --segment $seg --no-others --no-cpu-baseline --no-host-path --no-copy-ceiling --repeats 3 2> $OUT/r05s.err > $OUT/r05s_${w}_seg$seg.json
   python - $OUT/r05s_${w}_seg$seg.json $w $seg <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

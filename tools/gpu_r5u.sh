@@ -3,7 +3,7 @@
 OUT=$PWD/gpurun_out; mkdir -p $OUT; export TMPDIR=/tmp
 timeout 900 python -m pytest tests -m gpu -x -q -k "floor or vorbis" 2>&1 | grep -E "passed|failed|error" | tail -3
 for i in 1 2; do
-timeout 300 python bench.py --workload vorbisf --no-cpu-baseline --no-copy-ceiling --no-host-path --repeats 3 2> $OUT/r05u.err > $OUT/r05u_bench_vorbisf_$i.json
+timeout 300 python bench.py --full --workload vorbisf --no-cpu-baseline --no-copy-ceiling --no-host-path --repeats 3 2> $OUT/r05u.err > $OUT/r05u_bench_vorbisf_$i.json
 python - $OUT/r05u_bench_vorbisf_$i.json <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

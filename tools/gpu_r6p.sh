@@ -3,7 +3,7 @@
 OUT=$PWD/gpurun_out; mkdir -p $OUT; export TMPDIR=/tmp; REPO=$PWD
 timeout 900 python -m pytest tests/test_vorbis_floor_y.py tests/test_vorbis_decode.py tests/test_batcher_kinds.py tests/test_lookahead.py -x -q -m gpu 2>&1 | tail -5 | tee $OUT/r06p_gputest.txt
 for i in 1 2; do
-timeout 200 python bench.py --workload vorbisf --steps 200 --warmup 20 --no-cpu-baseline --no-host-path --no-others --no-copy-ceiling 2>/dev/null > $OUT/r06p_bench_vorbisf_$i.json
+timeout 200 python bench.py --full --workload vorbisf --steps 200 --warmup 20 --no-cpu-baseline --no-host-path --no-others --no-copy-ceiling 2>/dev/null > $OUT/r06p_bench_vorbisf_$i.json
 python -c "import json; d=json.load(open('$OUT/r06p_bench_vorbisf_$i.json')); print('vorbisf ms', d['ms_per_step'], 'frac', d['roofline']['frac'], 'verified', d.get('verified'))" | tee -a $OUT/r06p_gputest.txt
 done
 cd /tmp

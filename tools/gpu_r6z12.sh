@@ -9,7 +9,7 @@ print(sys.argv[2], "ms", round(d["ms_per_step"],4), "median", round(d["repeats"]
 PY
 }
 for w in aactns aacjs; do
-timeout 600 python bench.py --workload $w --no-others --no-cpu-baseline --no-host-path --no-copy-ceiling --repeats 2 > $OUT/r06z12_bench_$w.json 2> $OUT/r06z12_$w.err; show $OUT/r06z12_bench_$w.json $w
+timeout 600 python bench.py --full --workload $w --no-others --no-cpu-baseline --no-host-path --no-copy-ceiling --repeats 2 > $OUT/r06z12_bench_$w.json 2> $OUT/r06z12_$w.err; show $OUT/r06z12_bench_$w.json $w
 ( cd /tmp; timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_r06z12 -o $w -- python $OLDPWD/bench.py --workload $w --steps 20 --warmup 2 --no-cpu-baseline --no-host-path --no-others --no-copy-ceiling --repeats 0 > /dev/null 2>&1 )
 python tools/rocpd_summary.py gpurun_out/prof_r06z12/${w}_results.db > $OUT/r06z12_${w}_rocprofv3.txt 2>&1; head -9 $OUT/r06z12_${w}_rocprofv3.txt | cut -c1-200; rm -rf $OUT/prof_r06z12
 done

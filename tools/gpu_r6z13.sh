@@ -9,5 +9,5 @@ PY
 }
 for w in mp3 mp3q flac alac vorbis vorbisf; do for v in product ilp_all product ilp_all; do
   L=$PWD/build_ab/$v/libsymaccel.so; [ $v = product ] && L=$PWD/symphonia_amd/libsymaccel.so
-  SYMACCEL_LIB=$L timeout 300 python bench.py --workload $w --no-others --no-cpu-baseline --no-copy-ceiling --no-host-path --repeats 3 --steps 64 2> $OUT/r06z13.err > $OUT/r06z13_bench_${w}_$v.json; show $OUT/r06z13_bench_${w}_$v.json ${w}_$v
+  SYMACCEL_LIB=$L timeout 300 python bench.py --full --workload $w --no-others --no-cpu-baseline --no-copy-ceiling --no-host-path --repeats 3 --steps 64 2> $OUT/r06z13.err > $OUT/r06z13_bench_${w}_$v.json; show $OUT/r06z13_bench_${w}_$v.json ${w}_$v
 done; done

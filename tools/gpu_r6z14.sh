@@ -9,5 +9,5 @@ PY
 }
 for w in mp3q mp3; do for v in product mp3_MP3_PAIR_GROUP_1 mp3_MP3_PAIR_GROUP_9 mp3_MP3_FUSED_WG_WAVES_2 mp3_MP3_FUSED_WG_WAVES_8 mp3_MP3_FUSED_WG_WAVES_1 product; do
   L=$PWD/build_ab/$v/libsymaccel.so; [ $v = product ] && L=$PWD/symphonia_amd/libsymaccel.so
-  SYMACCEL_LIB=$L timeout 300 python bench.py --workload $w --no-others --no-cpu-baseline --no-copy-ceiling --no-host-path --repeats 3 --steps 64 2> $OUT/r06z14.err > $OUT/r06z14_bench_${w}_$v.json; show $OUT/r06z14_bench_${w}_$v.json ${w}_$v
+  SYMACCEL_LIB=$L timeout 300 python bench.py --full --workload $w --no-others --no-cpu-baseline --no-copy-ceiling --no-host-path --repeats 3 --steps 64 2> $OUT/r06z14.err > $OUT/r06z14_bench_${w}_$v.json; show $OUT/r06z14_bench_${w}_$v.json ${w}_$v
 done; done

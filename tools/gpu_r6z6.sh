@@ -8,12 +8,12 @@ d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 print(sys.argv[2], "ms", round(d["ms_per_step"],4), "median", round(d["repeats"]["ms_per_step_median"],4) if d.get("repeats") else None, "frac", round(d["roofline"]["frac"],4), "verified", (d.get("verified") or {}).get("mismatches"))
 PY
 }
-timeout 600 python bench.py --workload aactns --no-others --no-cpu-baseline --no-host-path --no-copy-ceiling --repeats 2 > $OUT/r06z6_bench_aactns.json 2> $OUT/r06z6_aactns.err; show $OUT/r06z6_bench_aactns.json aactns
+timeout 600 python bench.py --full --workload aactns --no-others --no-cpu-baseline --no-host-path --no-copy-ceiling --repeats 2 > $OUT/r06z6_bench_aactns.json 2> $OUT/r06z6_aactns.err; show $OUT/r06z6_bench_aactns.json aactns
 ( cd /tmp; timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_r06z6_aactns -o aactns -- python $OLDPWD/bench.py --workload aactns --steps 10 --warmup 2 --no-cpu-baseline --no-host-path --no-others --no-copy-ceiling --repeats 0 > /dev/null 2>&1 )
 python tools/rocpd_summary.py gpurun_out/prof_r06z6_aactns/aactns_results.db > $OUT/r06z6_aactns_rocprofv3.txt 2>&1; head -12 $OUT/r06z6_aactns_rocprofv3.txt | cut -c1-200; rm -rf $OUT/prof_r06z6_aactns
 for v in product mp3f_12_3 mp3f_16_4 mp3f_8_2 mp3f_6_3; do
   L=$PWD/build_ab/$v/libsymaccel.so; [ $v = product ] && L=$PWD/symphonia_amd/libsymaccel.so
-  SYMACCEL_LIB=$L timeout 300 python bench.py --workload mp3q --no-others --no-cpu-baseline --no-copy-ceiling --no-host-path --repeats 3 --steps 64 2> $OUT/r06z6_mp3q_$v.err > $OUT/r06z6_bench_mp3q_$v.json; show $OUT/r06z6_bench_mp3q_$v.json mp3q_$v
+  SYMACCEL_LIB=$L timeout 300 python bench.py --full --workload mp3q --no-others --no-cpu-baseline --no-copy-ceiling --no-host-path --repeats 3 --steps 64 2> $OUT/r06z6_mp3q_$v.err > $OUT/r06z6_bench_mp3q_$v.json; show $OUT/r06z6_bench_mp3q_$v.json mp3q_$v
 done
 B=symphonia_amd/build/decoders_bench
 export LD_LIBRARY_PATH=$PWD/symphonia_amd:$LD_LIBRARY_PATH

@@ -23,12 +23,12 @@ python -m pytest tests -m gpu -q 2>&1 | grep -v -E "^(RCCL|HIP|ROCm|Hostname|Lib
 cat $OUT/gputest_${TAG}.log
 python tools/collect_round.py $TAG --traffic-only
 for w in aac mp3 vorbis flac alac mp3q vorbisf aacjs aactns flacp alacp; do
-  timeout 300 python bench.py --workload $w --steps 20 --warmup 3 --no-others > $OUT/bench_$w.json 2> $OUT/bench_$w.err
+  timeout 300 python bench.py --full --workload $w --steps 20 --warmup 3 --no-others > $OUT/bench_$w.json 2> $OUT/bench_$w.err
   echo "bench $w rc=$?"; tail -n 1 $OUT/bench_$w.json | cut -c1-300
 done
 python tools/collect_round.py $TAG --stage
 cp $OUT/gputest_${TAG}.log $OUT/profiles_${TAG}/${TAG}_gputest.log
 # the exact default command (what the driver runs): headline + other_workloads + same-run copy ceilings
-timeout 600 python bench.py > $OUT/profiles_${TAG}/${TAG}_default_bench.json 2> $OUT/bench_default.err
+timeout 600 python bench.py --full > $OUT/profiles_${TAG}/${TAG}_default_bench.json 2> $OUT/bench_default.err
 echo "default bench rc=$?"; cut -c1-600 $OUT/profiles_${TAG}/${TAG}_default_bench.json
 rm -rf $OUT/prof_${TAG}_*/ $OUT/pmc_${TAG}_*/   # the rocpd databases: too large to copy back
