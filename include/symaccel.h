@@ -52,7 +52,7 @@
 extern "C" {
 #endif
 
-#define SYMACCEL_ABI_VERSION 8 /* 2: *_pp_device entry points, per-block status arrays, lookahead staging; 3: multi-GPU, probe; 4: mp3_decode_*device, vorbis floor_y; 5: aac_decode_pipelined, aac_joint_stereo_list, vorbis_decode; 6: batcher; 7: batch kinds for Vorbis from posts, FLAC and ALAC (symaccel_batch_slot has six input planes), lanes, per-ticket status; 8: *_strided_device (padded row pitch for the FLAC / ALAC planes), symaccel_row_stride */
+#define SYMACCEL_ABI_VERSION 8 /* 2: *_pp_device entry points, per-block status arrays, lookahead staging; 3: multi-GPU, probe; 4: mp3_decode_*device, vorbis floor_y; 5: aac_decode_pipelined, aac_joint_stereo_list, vorbis_decode; 6: batcher; 7: batch kinds for Vorbis from posts, FLAC and ALAC (symaccel_batch_slot has six input planes), lanes, per-ticket status; 8: *_strided_device (padded row pitch for the FLAC / ALAC planes), symaccel_row_stride; additions within 8: symaccel_md5_*, symaccel_flac_md5(_device) (STREAMINFO MD5) */
 
 typedef enum symaccel_status {
     SYMACCEL_OK = 0,
@@ -600,6 +600,56 @@ int symaccel_flac_decorrelate_device(symaccel_ctx *ctx, const uint8_t *d_mode, i
                                      uint32_t out_shift);
 int symaccel_flac_decorrelate(symaccel_ctx *ctx, const uint8_t *h_mode, int32_t *h_ch0, int32_t *h_ch1,
                               size_t n_pairs, size_t blocksize, uint32_t out_shift);
+
+/* FLAC stream verification: the MD5 of STREAMINFO (symphonia-bundle-flac/src/validate.rs:25-75, decoder.rs:231-234, 272-308).
+ * symaccel_md5_state is the running state of symphonia-core's Md5 (checksum/md5.rs:172-176): abcd, the number of bytes hashed,
+ * and the first len % 64 bytes of the block being filled (the rest of `tail` is zero in every state this library writes). */
+typedef struct symaccel_md5_state {
+    uint32_t abcd[4];
+    uint64_t len;
+    uint8_t tail[64];
+} symaccel_md5_state;
+/* Host arithmetic, no context.  digest() pads a copy: the state goes on (md5.rs:193-232).  digest: 16 bytes. */
+int symaccel_md5_init(symaccel_md5_state *state);
+int symaccel_md5_update(symaccel_md5_state *state, const void *bytes, size_t n);
+int symaccel_md5_digest(const symaccel_md5_state *state, uint8_t *digest);
+/* One frame of a verified stream: block length (samples per channel, <= the job's row_pitch; 0 hashes nothing), the pair mode
+ * of symaccel_flac_decorrelate_device (0 independent, 1 left/side, 2 mid/side, 3 right/side; non-zero only with nch == 2), and the
+ * frame's own bytes per sample, ceil(bps / 8) of its header (decoder.rs:148-151: a frame header may carry a width of its own), 1..4;
+ * 0 = the job's (the header defers to STREAMINFO). */
+typedef struct symaccel_flac_md5_frame {
+    uint16_t block_len;
+    uint8_t pair_mode;
+    uint8_t bytes_per_sample;
+} symaccel_flac_md5_frame;
+/* One stream: frame f's channel c is the row rows + (f * nch + c) * row_pitch (the restored subframe, BEFORE decorrelation and
+ * the `<< (32 - bps)`, decoder.rs:239-242: what the reference hashes).  Every frame, in order, is decorrelated as it is read,
+ * truncated to bytes_per_sample little-endian bytes, interleaved by channel (validate.rs copy_as_i8 / i16 / i24 / i32) and fed
+ * to the MD5 that starts from *state; *state receives the state after the last frame, checkpoints[f] (NULL: none) the state
+ * after frame f.  nch 1..8; bytes_per_sample (the stream's, for frames that name none) 1..4, 0 = hash nothing (validate.rs:39:
+ * bps 0).  `state` must be a device pointer (a job whose state is NULL is skipped: nothing read, nothing written); `rows`, `frames`
+ * and `checkpoints` (NULL: none) must cover what the job describes. */
+typedef struct symaccel_flac_md5_job {
+    const int32_t *rows;
+    const symaccel_flac_md5_frame *frames;
+    symaccel_md5_state *state;
+    symaccel_md5_state *checkpoints;
+    uint64_t row_pitch;
+    uint32_t n_frames;
+    uint8_t nch;
+    uint8_t bytes_per_sample;
+    uint8_t pad[2];
+} symaccel_flac_md5_job;
+/* n_jobs streams in one launch, one WAVEFRONT each (MD5 is a serial chain within a stream; streams are independent).  d_jobs and
+ * every pointer in it are device memory.  A job whose description does not add up (nch outside 1..8, a bytes_per_sample above 4,
+ * a block longer than row_pitch, a pair mode above 3 or a pair mode with nch != 2, NULL rows, NULL frames with n_frames > 0)
+ * hashes nothing: its state stays as it was and its checkpoints are that state. */
+int symaccel_flac_md5_device(symaccel_ctx *ctx, const symaccel_flac_md5_job *d_jobs, size_t n_jobs);
+/* The same for one stream in host memory (rows back to back at row_pitch); SYMACCEL_ERR_INVALID_ARG for a job that does not add
+ * up.  h_checkpoints may be NULL. */
+int symaccel_flac_md5(symaccel_ctx *ctx, const int32_t *h_rows, size_t row_pitch, const symaccel_flac_md5_frame *h_frames,
+                      size_t n_frames, int nch, int bytes_per_sample, symaccel_md5_state *h_state_io,
+                      symaccel_md5_state *h_checkpoints);
 
 /* --------------------------------------------------------------------------------- ALAC */
 

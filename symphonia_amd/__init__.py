@@ -9,7 +9,9 @@ from .backend import (PinnedBuffer, Batcher, BatchSlot, BATCH_AAC_SYNTH, BATCH_M
                       AacDsp, AacSpectralTools, VORBIS_FLOOR1_DTYPE, AAC_JS_DTYPE, AAC_TNS_DTYPE, AAC_JS_MS, AAC_JS_INTENSITY, AlacPredictor, Context, Fft, FlacPredictor, Ifft, Imdct, Mp3Requantize, Mp3Stereo, Mp3Synthesis, MpaPolyphase, VorbisDsp,  # noqa: F401
                       MP3_REQUANT_DTYPE, MP3_RQ_PREFLAG, MP3_RQ_SCALEFAC_SCALE, MP3_STEREO_DTYPE, MP3_ST_MID_SIDE, MP3_ST_INTENSITY,
                       MP3_ST_MPEG1, MP3_ST_IS_SCALE,
-                      aac_side, alac_desc, flac_desc, mp3_side, FLAC_FIXED, FLAC_LPC, FLAC_VERBATIM)
+                      aac_side, alac_desc, flac_desc, mp3_side, FLAC_FIXED, FLAC_LPC, FLAC_VERBATIM,
+                      MD5_STATE_DTYPE, FLAC_MD5_FRAME_DTYPE, FLAC_MD5_JOB_DTYPE, flac_bytes_per_sample, md5_init, md5_update, md5_digest, flac_md5_frames, flac_md5,
+                      flac_md5_device)
 
 __all__ = ["Library", "SymaccelError", "default_library", "Context", "Imdct", "Fft", "Ifft", "AacDsp", "AacSpectralTools", "Mp3Synthesis", "Mp3Requantize", "Mp3Stereo", "MpaPolyphase",
            "VorbisDsp", "FlacPredictor", "AlacPredictor", "aac_side", "mp3_side", "flac_desc", "alac_desc"]

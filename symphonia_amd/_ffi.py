@@ -55,6 +55,7 @@ ABI_SYMBOLS = [
     "symaccel_batcher_get_stats", "symaccel_batcher_configure", "symaccel_batcher_last_error", "symaccel_batcher_vorbis_floor",
     "symaccel_batcher_submit_vorbis_decode", "symaccel_batcher_submit_flac_restore", "symaccel_batcher_submit_alac_predict",
     "symaccel_flac_restore_strided_device", "symaccel_alac_predict_strided_device", "symaccel_row_stride",
+    "symaccel_md5_init", "symaccel_md5_update", "symaccel_md5_digest", "symaccel_flac_md5_device", "symaccel_flac_md5",
 ]
 
 _vp, _sz, _i, _d, _u32 = C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.c_uint32
@@ -219,6 +220,11 @@ class Library:
         d.symaccel_host_vorbis_floor0_coeffs.argtypes = [_vp, _i]
         d.symaccel_host_vorbis_floor0.argtypes = [_vp, _i, _vp, _u32, C.c_uint16, C.c_uint8, C.c_uint8, C.c_uint64, _vp]
         d.symaccel_flac_block_status_device.argtypes = [_vp, _vp, _sz, _sz, _vp]
+        d.symaccel_md5_init.argtypes = [_vp]
+        d.symaccel_md5_update.argtypes = [_vp, _vp, _sz]
+        d.symaccel_md5_digest.argtypes = [_vp, _vp]
+        d.symaccel_flac_md5_device.argtypes = [_vp, _vp, _sz]
+        d.symaccel_flac_md5.argtypes = [_vp, _vp, _sz, _vp, _sz, _i, _i, _vp, _vp]
         d.symaccel_alac_block_status_device.argtypes = [_vp, _vp, _sz, _vp]
         d.symaccel_vorbis_floor1_status_device.argtypes = [_vp, _i, _vp, _sz, _vp]
         d.symaccel_aac_tns_status_device.argtypes = [_vp, _sz, _vp, _sz, _vp]

@@ -632,6 +632,77 @@ class FlacPredictor:
                        int(blocksize), int(out_shift))
 
 
+# STREAMINFO MD5 verification (validate.rs:25-75): symaccel_md5_state / symaccel_flac_md5_frame / symaccel_flac_md5_job
+MD5_STATE_DTYPE = np.dtype([("abcd", np.uint32, (4,)), ("len", np.uint64), ("tail", np.uint8, (64,))])
+FLAC_MD5_FRAME_DTYPE = np.dtype([("block_len", np.uint16), ("pair_mode", np.uint8), ("bytes_per_sample", np.uint8)])
+FLAC_MD5_JOB_DTYPE = np.dtype([("rows", np.uint64), ("frames", np.uint64), ("state", np.uint64), ("checkpoints", np.uint64),
+                               ("row_pitch", np.uint64), ("n_frames", np.uint32), ("nch", np.uint8), ("bytes_per_sample", np.uint8),
+                               ("pad", np.uint8, (2,))])
+
+
+def flac_bytes_per_sample(bps):
+    """validate.rs:39-45: bits per sample rounded up to whole bytes (0 = hash nothing)."""
+    return (int(bps) + 7) // 8
+
+
+def md5_init(lib=None):
+    """A fresh symaccel_md5_state (one record of MD5_STATE_DTYPE)."""
+    lib = lib if lib is not None else _ffi.default_library()
+    st = np.zeros(1, MD5_STATE_DTYPE)
+    lib.check(lib.dll.symaccel_md5_init(st.ctypes.data))
+    return st
+
+
+def md5_update(state, data, lib=None):
+    """Feed bytes to a state in place (host arithmetic)."""
+    lib = lib if lib is not None else _ffi.default_library()
+    b = np.frombuffer(bytes(data), np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data).view(np.uint8).ravel()
+    lib.check(lib.dll.symaccel_md5_update(state.ctypes.data, b.ctypes.data if b.size else None, b.size))
+    return state
+
+
+def md5_digest(state, lib=None):
+    """The 16-byte digest of a state; the state goes on (md5.rs:193-232)."""
+    lib = lib if lib is not None else _ffi.default_library()
+    out = np.zeros(16, np.uint8)
+    lib.check(lib.dll.symaccel_md5_digest(np.ascontiguousarray(state).ctypes.data, out.ctypes.data))
+    return out.tobytes()
+
+
+def flac_md5_frames(block_len, pair_mode=None, bytes_per_sample=None):
+    """FLAC_MD5_FRAME_DTYPE records; bytes_per_sample per frame (0 = the stream's) when a frame header names a width of its own."""
+    bl = np.asarray(block_len)
+    fr = np.zeros(bl.shape, FLAC_MD5_FRAME_DTYPE)
+    fr["block_len"] = bl
+    if pair_mode is not None:
+        fr["pair_mode"] = np.asarray(pair_mode)
+    if bytes_per_sample is not None:
+        fr["bytes_per_sample"] = np.asarray(bytes_per_sample)
+    return fr
+
+
+def flac_md5(ctx, rows, frames, nch, bytes_per_sample, state=None, checkpoints=False):
+    """symaccel_flac_md5: one stream in host memory.  rows[n_frames * nch, row_pitch] i32 (frame f's channel c in row f * nch + c,
+    restored, before decorrelation and the final shift), frames: FLAC_MD5_FRAME_DTYPE[n_frames].  Returns the state after the last
+    frame, and with checkpoints=True also the state after every frame."""
+    r = _np(rows, np.int32)
+    fr = np.ascontiguousarray(frames, FLAC_MD5_FRAME_DTYPE)
+    if fr.size and 1 <= int(nch) <= 8 and (r.ndim != 2 or r.shape[0] < fr.size * int(nch)):  # the C side reads n_frames * nch rows (it refuses other nch)
+        raise ValueError("rows must be [n_frames * nch, row_pitch]: %d frames x %d channels, got shape %s" % (fr.size, int(nch), r.shape))
+    st = (md5_init(ctx.lib) if state is None else np.array(state, MD5_STATE_DTYPE).reshape(1)).copy()
+    cps = np.zeros(fr.size, MD5_STATE_DTYPE) if checkpoints else None
+    ctx._call(ctx.lib.dll.symaccel_flac_md5, _ptr(r), int(r.shape[1]) if r.ndim == 2 else 0, _ptr(fr), fr.size, int(nch), int(bytes_per_sample),
+              st.ctypes.data, _ptr(cps))
+    return (st, cps) if checkpoints else st
+
+
+def flac_md5_device(ctx, jobs, n_jobs=None):
+    """symaccel_flac_md5_device: jobs = FLAC_MD5_JOB_DTYPE records in device memory (a torch uint8 tensor), every pointer in them
+    device memory; one lane per job."""
+    n = int(n_jobs) if n_jobs is not None else (jobs.numel() if _is_torch(jobs) else jobs.nbytes) // FLAC_MD5_JOB_DTYPE.itemsize
+    ctx._call(ctx.lib.dll.symaccel_flac_md5_device, _ptr(jobs), n)
+
+
 ALAC_DESC_DTYPE = np.dtype([("mode", np.uint8), ("lpc_order", np.uint8), ("shift", np.uint8), ("bps", np.uint8)])
 
 

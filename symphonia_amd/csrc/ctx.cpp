@@ -1110,6 +1110,49 @@ int symaccel_flac_decorrelate_device(symaccel_ctx *ctx, const uint8_t *d_mode, i
     return launch_flac_decorrelate(ctx, d_mode, d_ch0, d_ch1, n_pairs, blocksize, out_shift);
 }
 
+int symaccel_flac_md5_device(symaccel_ctx *ctx, const symaccel_flac_md5_job *d_jobs, size_t n_jobs) {
+    if (!ctx) return SYMACCEL_ERR_INVALID_ARG;
+    if (n_jobs == 0) return SYMACCEL_OK;
+    if (!d_jobs) return SYMACCEL_ERR_INVALID_ARG;
+    DeviceGuard dev(ctx);
+    if (!dev.ok()) return dev.status();
+    return launch_flac_md5(ctx, d_jobs, n_jobs);
+}
+
+int symaccel_flac_md5(symaccel_ctx *ctx, const int32_t *h_rows, size_t row_pitch, const symaccel_flac_md5_frame *h_frames, size_t n_frames,
+                      int nch, int bytes_per_sample, symaccel_md5_state *h_state_io, symaccel_md5_state *h_checkpoints) {
+    if (!ctx || !h_state_io || nch < 1 || nch > 8 || bytes_per_sample < 0 || bytes_per_sample > 4 || n_frames > 0xffffffffu)
+        return SYMACCEL_ERR_INVALID_ARG;
+    if (n_frames == 0) return SYMACCEL_OK;
+    if (!h_frames || !h_rows) return SYMACCEL_ERR_INVALID_ARG;
+    for (size_t f = 0; f < n_frames; ++f) {  // what the kernel would refuse (validate.rs sees decoded frames only)
+        const symaccel_flac_md5_frame &fr = h_frames[f];
+        if (fr.block_len > row_pitch || fr.pair_mode > 3 || (fr.pair_mode != 0 && nch != 2) || fr.bytes_per_sample > 4) return SYMACCEL_ERR_INVALID_ARG;
+    }
+    DeviceGuard dev(ctx);
+    if (!dev.ok()) return dev.status();
+    const size_t row_bytes = n_frames * (size_t)nch * row_pitch * 4;
+    DevBuf rows(ctx), frames(ctx), state(ctx), cps(ctx), job(ctx);
+    SYM_TRY(rows.from_host(h_rows, row_bytes));
+    SYM_TRY(frames.from_host(h_frames, n_frames * sizeof(symaccel_flac_md5_frame)));
+    SYM_TRY(state.from_host(h_state_io, sizeof(symaccel_md5_state)));
+    if (h_checkpoints) SYM_TRY(cps.alloc(n_frames * sizeof(symaccel_md5_state)));
+    symaccel_flac_md5_job j{};
+    j.rows = (const int32_t *)rows.p;
+    j.frames = (const symaccel_flac_md5_frame *)frames.p;
+    j.state = (symaccel_md5_state *)state.p;
+    j.checkpoints = h_checkpoints ? (symaccel_md5_state *)cps.p : nullptr;
+    j.row_pitch = row_pitch;
+    j.n_frames = (uint32_t)n_frames;
+    j.nch = (uint8_t)nch;
+    j.bytes_per_sample = (uint8_t)bytes_per_sample;
+    SYM_TRY(job.from_host(&j, sizeof j));
+    SYM_TRY(launch_flac_md5(ctx, (const symaccel_flac_md5_job *)job.p, 1));
+    SYM_TRY(state.to_host(h_state_io, sizeof(symaccel_md5_state)));
+    if (h_checkpoints) SYM_TRY(cps.to_host(h_checkpoints, n_frames * sizeof(symaccel_md5_state)));
+    return symaccel_sync(ctx);
+}
+
 // ---- per-record status arrays --------------------------------------------------------------
 
 int symaccel_flac_block_status_device(symaccel_ctx *ctx, const symaccel_flac_desc *d_desc, size_t n_blocks, size_t blocksize,

@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "lane_tiles.h"
+#include "md5_block.h"
 
 namespace symaccel {
 
@@ -378,7 +379,141 @@ __global__ void flac_decorrelate_kernel(const uint8_t *__restrict__ mode, int32_
     }
 }
 
+// ---- STREAMINFO MD5 (validate.rs:25-75 over decoder.rs:199-234's pre-shift samples) ----------------------------------------------
+// One WAVEFRONT per stream: MD5 is a serial chain inside a stream, streams are independent.  The wavefront walks the stream's
+// frames in chunks of 64 sample-frames, one per lane: a lane loads its sample of every channel row (each row access is one
+// coalesced 256-byte request across the wavefront, the next chunk's already in flight while the current one is hashed),
+// decorrelates the pair, and writes the samples' bytes_per_sample low bytes, interleaved by channel, at their place in a byte
+// buffer in LDS behind the bytes still pending from before.  Then the chain runs over every complete 64-byte block of the buffer on
+// wave-uniform values (the 16 words read from LDS and made scalar: the arithmetic goes to the scalar unit), and the incomplete rest
+// moves to the front.  The state after every frame is written out as a checkpoint.
+constexpr int kMd5Chunk = 64;                                 // sample-frames per chunk, one per lane
+constexpr int kMd5BufBytes = 64 + kMd5Chunk * 8 * 4 + 64;     // pending (< 64) + one chunk of 8 channels x 4 bytes, rounded up
+
+__device__ __forceinline__ uint32_t md5_uniform(uint32_t v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_readfirstlane(v);
+#else
+    return v;
+#endif
+}
+
+__device__ __forceinline__ void md5_decorrelate(unsigned mode, int32_t &a, int32_t &b) {  // decoder.rs:32-82, as flac_decorrelate_kernel
+    if (mode == 1) {
+        b = (int32_t)((uint32_t)a - (uint32_t)b);
+    } else if (mode == 2) {
+        const int32_t mid = (int32_t)(((uint32_t)a << 1) | ((uint32_t)b & 1u));
+        const int32_t sd = b;
+        a = (int32_t)((uint32_t)mid + (uint32_t)sd) >> 1;
+        b = (int32_t)((uint32_t)mid - (uint32_t)sd) >> 1;
+    } else if (mode == 3) {
+        a = wrap_add(a, b);
+    }
+}
+
+// the state as symaccel_md5_state: lane 0 writes abcd and len, lanes 0..15 one word of the tail each (the pending bytes, then zeros)
+__device__ __forceinline__ void md5_store(const uint32_t (&abcd)[4], uint64_t len, const uint8_t *buf, unsigned pend, symaccel_md5_state *out, int lane) {
+    uint32_t *o = reinterpret_cast<uint32_t *>(out);
+    if (lane == 0) {
+        *reinterpret_cast<uint2 *>(o) = make_uint2(abcd[0], abcd[1]);
+        *reinterpret_cast<uint2 *>(o + 2) = make_uint2(abcd[2], abcd[3]);
+        *reinterpret_cast<uint64_t *>(o + 4) = len;
+    }
+    if (lane < 16) {
+        uint32_t w = 0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const unsigned at = 4u * (unsigned)lane + (unsigned)q;
+            if (at < pend) w |= (uint32_t)buf[at] << (8 * q);
+        }
+        o[6 + lane] = w;
+    }
+}
+
+__global__ __launch_bounds__(64) void flac_md5_kernel(const symaccel_flac_md5_job *__restrict__ jobs) {
+    __shared__ __attribute__((aligned(16))) uint8_t buf[kMd5BufBytes];
+    const int lane = (int)threadIdx.x;
+    const symaccel_flac_md5_job job = jobs[blockIdx.x];
+    if (job.state == nullptr) return;  // nowhere to start from or to write to: skipped
+    // the job is checked before anything is hashed: one that does not add up hashes nothing
+    const unsigned nch = job.nch;
+    bool ok = nch >= 1 && nch <= 8 && job.bytes_per_sample <= 4 && job.rows != nullptr && (job.n_frames == 0 || job.frames != nullptr);
+    for (uint32_t f0 = 0; ok && f0 < job.n_frames; f0 += 64) {  // the frame table, 64 entries per step
+        const uint32_t f = f0 + (uint32_t)lane;
+        bool bad = false;
+        if (f < job.n_frames) {
+            const symaccel_flac_md5_frame fr = job.frames[f];
+            bad = fr.block_len > job.row_pitch || fr.pair_mode > 3 || (fr.pair_mode != 0 && nch != 2) || fr.bytes_per_sample > 4;
+        }
+        ok = wave_max(bad ? 1u : 0u) == 0u;
+    }
+    const symaccel_md5_state *st = job.state;
+    uint32_t abcd[4] = {md5_uniform(st->abcd[0]), md5_uniform(st->abcd[1]), md5_uniform(st->abcd[2]), md5_uniform(st->abcd[3])};
+    uint64_t len = st->len;
+    unsigned pend = (unsigned)(len & 63);
+    if (lane < (int)pend) buf[lane] = st->tail[lane];
+    __syncthreads();
+    for (uint32_t f = 0; f < job.n_frames; ++f) {
+        if (ok) {
+            const symaccel_flac_md5_frame fr = job.frames[f];
+            const unsigned nb = fr.bytes_per_sample ? fr.bytes_per_sample : job.bytes_per_sample;  // the frame's width, else the stream's
+            const unsigned n = nb ? fr.block_len : 0u, mode = fr.pair_mode, stride = nch * nb;
+            const int32_t *row0 = job.rows + (size_t)f * nch * job.row_pitch;
+            int32_t x[8], nx[8];
+            auto load = [&](unsigned i0, int32_t (&v)[8]) {
+                const unsigned i = i0 + (unsigned)lane;
+#pragma unroll
+                for (int c = 0; c < 8; ++c) v[c] = ((unsigned)c < nch && i < n) ? row0[(size_t)c * job.row_pitch + i] : 0;
+            };
+            if (n) load(0, nx);
+            for (unsigned i0 = 0; i0 < n; i0 += kMd5Chunk) {
+#pragma unroll
+                for (int c = 0; c < 8; ++c) x[c] = nx[c];
+                if (i0 + kMd5Chunk < n) load(i0 + kMd5Chunk, nx);  // in flight while this chunk is hashed
+                const unsigned cnt = min((unsigned)kMd5Chunk, n - i0);
+                if ((unsigned)lane < cnt) {
+                    if (mode) md5_decorrelate(mode, x[0], x[1]);
+                    uint8_t *p = buf + pend + (unsigned)lane * stride;
+#pragma unroll
+                    for (int c = 0; c < 8; ++c)
+                        if ((unsigned)c < nch) {
+                            const uint32_t v = (uint32_t)x[c];
+#pragma unroll
+                            for (int q = 0; q < 4; ++q)
+                                if ((unsigned)q < nb) p[(unsigned)c * nb + (unsigned)q] = (uint8_t)(v >> (8 * q));
+                        }
+                }
+                __syncthreads();
+                const unsigned total = pend + cnt * stride, nblk = total / 64;
+                for (unsigned b = 0; b < nblk; ++b) {
+                    const uint32_t *w = reinterpret_cast<const uint32_t *>(buf + 64 * b);
+                    uint32_t m[16];
+#pragma unroll
+                    for (int k = 0; k < 16; ++k) m[k] = md5_uniform(w[k]);
+                    md5_block(abcd, m);
+                }
+                const unsigned rest = total - 64 * nblk;
+                const uint8_t carry = (unsigned)lane < rest ? buf[64 * nblk + (unsigned)lane] : 0;
+                __syncthreads();
+                if ((unsigned)lane < rest) buf[lane] = carry;
+                __syncthreads();
+                pend = rest;
+            }
+            len += (uint64_t)n * stride;
+        }
+        if (job.checkpoints) md5_store(abcd, len, buf, pend, job.checkpoints + f, lane);
+    }
+    if (ok) md5_store(abcd, len, buf, pend, job.state, lane);
+}
+
 }  // namespace
+
+int launch_flac_md5(symaccel_ctx *ctx, const symaccel_flac_md5_job *d_jobs, size_t n_jobs) {
+    if (n_jobs > 0x7fffffffu) return SYMACCEL_ERR_INVALID_ARG;
+    hipLaunchKernelGGL(flac_md5_kernel, dim3((unsigned)n_jobs), dim3(64), 0, ctx->stream, d_jobs);  // one wavefront per job
+    SYM_GPU(ctx, hipGetLastError());
+    return SYMACCEL_OK;
+}
 
 int launch_flac_restore(symaccel_ctx *ctx, int32_t *d_buf, const symaccel_flac_desc *d_desc, const int32_t *d_coeffs,
                         size_t n_blocks, size_t blocksize, const uint8_t *d_pair_mode, uint32_t out_shift, size_t stride) {

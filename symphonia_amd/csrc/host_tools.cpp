@@ -10,11 +10,16 @@
 //   Floor0::read_channel (2 cos step)   floor.rs:246-248
 //   Floor0::synthesis                   floor.rs:262-340
 //   linear_floor0_value                 floor.rs:379-390
+// And the MD5 a FLAC stream is verified with (symphonia-core/src/checksum/md5.rs): the per-stream running state the
+// verification kernel (flac.hip) starts from and hands back, and the digest of it.
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <limits>
 
 #include "../../include/symaccel.h"
+#include "md5_block.h"
 
 namespace {
 
@@ -132,6 +137,62 @@ int symaccel_host_vorbis_floor0(const float *h_coeffs, int order, const int32_t 
         while (i < n && h_map[i] == iter_cond) h_floor[i++] = value;
         if (i >= n) break;
     }
+    return SYMACCEL_OK;
+}
+
+
+// ---- MD5 (md5.rs:172-278) ------------------------------------------------------------------
+
+namespace {
+void md5_block_bytes(uint32_t (&abcd)[4], const uint8_t *p) {
+    uint32_t m[16];
+    for (int k = 0; k < 16; ++k)
+        m[k] = (uint32_t)p[4 * k] | (uint32_t)p[4 * k + 1] << 8 | (uint32_t)p[4 * k + 2] << 16 | (uint32_t)p[4 * k + 3] << 24;
+    symaccel::md5_block(abcd, m);
+}
+}  // namespace
+
+int symaccel_md5_init(symaccel_md5_state *state) {
+    if (!state) return SYMACCEL_ERR_INVALID_ARG;
+    *state = symaccel_md5_state{};
+    state->abcd[0] = 0x67452301u;  // md5.rs:180-185
+    state->abcd[1] = 0xefcdab89u;
+    state->abcd[2] = 0x98badcfeu;
+    state->abcd[3] = 0x10325476u;
+    return SYMACCEL_OK;
+}
+
+int symaccel_md5_update(symaccel_md5_state *state, const void *bytes, size_t n) {
+    if (!state || (n && !bytes)) return SYMACCEL_ERR_INVALID_ARG;
+    const uint8_t *p = static_cast<const uint8_t *>(bytes);
+    size_t have = (size_t)(state->len & 63);
+    state->len += n;
+    if (have) {  // complete the block the state holds the front of
+        const size_t take = std::min(n, 64 - have);
+        std::memcpy(state->tail + have, p, take);
+        p += take;
+        n -= take;
+        have += take;
+        if (have < 64) return SYMACCEL_OK;
+        md5_block_bytes(state->abcd, state->tail);
+    }
+    for (; n >= 64; p += 64, n -= 64) md5_block_bytes(state->abcd, p);
+    std::memset(state->tail, 0, sizeof state->tail);
+    std::memcpy(state->tail, p, n);
+    return SYMACCEL_OK;
+}
+
+int symaccel_md5_digest(const symaccel_md5_state *state, uint8_t *digest) {
+    if (!state || !digest) return SYMACCEL_ERR_INVALID_ARG;
+    symaccel_md5_state s = *state;  // md5.rs:193-232: padding goes into a copy, the running state is not consumed
+    const uint64_t bits = s.len * 8;
+    uint8_t pad[72] = {0x80};
+    const size_t have = (size_t)(s.len & 63);
+    const size_t n_pad = (have < 56 ? 56 : 120) - have;
+    for (int k = 0; k < 8; ++k) pad[n_pad + k] = (uint8_t)(bits >> (8 * k));
+    symaccel_md5_update(&s, pad, n_pad + 8);
+    for (int k = 0; k < 4; ++k)
+        for (int q = 0; q < 4; ++q) digest[4 * k + q] = (uint8_t)(s.abcd[k] >> (8 * q));
     return SYMACCEL_OK;
 }
 

@@ -296,5 +296,7 @@ int launch_batch_flag(symaccel_ctx *ctx, hipStream_t stream, uint64_t *h_flag, u
 int launch_probe_copy(symaccel_ctx *ctx, const void *d_src, void *d_dst, size_t bytes, unsigned frames_per_wavefront, unsigned flags);
 int launch_flac_decorrelate(symaccel_ctx *ctx, const uint8_t *d_mode, int32_t *d_ch0, int32_t *d_ch1,
                             size_t n_pairs, size_t blocksize, uint32_t out_shift);
+// flac.hip: STREAMINFO MD5, one lane per job (d_jobs and everything it points to on the device)
+int launch_flac_md5(symaccel_ctx *ctx, const symaccel_flac_md5_job *d_jobs, size_t n_jobs);
 
 }  // namespace symaccel
