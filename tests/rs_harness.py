@@ -115,6 +115,105 @@ AAC_FILES = ("common.rs", "window.rs", "dsp.rs", "ics/gain.rs", "ics/ltp.rs", "i
 CORE_DSP = ("dsp/fft/mod.rs", "dsp/fft/no_simd.rs", "dsp/mdct.rs")  # the in-tree transform: what the product reproduces
 
 
+# ---- the reference's own `#[test]` functions (tests/test_reference_unit_tests.py)
+_CORE = "symphonia-core/src/"
+_AAC = "symphonia-codec-aac/src/aac/"
+_MP3 = "symphonia-bundle-mp3/src/"
+# file with `#[test]`s -> what is loaded before it: "IO" (CORE_IO + io/bit.rs with expand_vlc_entries, as Harness(reference=True) does),
+# sibling files of the reference tree, files of tests/rust/ (own text).  The file itself is loaded last: every `#[cfg(test)] mod tests`
+# registers as `tests::<name>` (rsinterp/interp.py register_items), so the last one loaded is the one `tests::` names.
+REFERENCE_TEST_SIBLINGS = {
+    _CORE + "dsp/fft/mod.rs": (_CORE + "dsp/fft/no_simd.rs",),
+    _CORE + "dsp/mdct.rs": (_CORE + "dsp/fft/mod.rs", _CORE + "dsp/fft/no_simd.rs"),
+    _MP3 + "layer3/hybrid_synthesis.rs": ("IO", _MP3 + "common.rs", _MP3 + "header.rs", _MP3 + "layer3/common.rs"),
+    _MP3 + "synthesis.rs": (),
+    "symphonia-bundle-flac/src/decoder.rs": ("IO", "symphonia-bundle-flac/src/frame.rs"),
+    "symphonia-bundle-flac/src/frame.rs": ("IO",),
+    "symphonia-codec-vorbis/src/codebook.rs": ("IO", "symphonia-codec-vorbis/src/common.rs"),
+    "symphonia-codec-vorbis/src/common.rs": (),
+    _AAC + "ics/mod.rs": ("IO", "symphonia-common/src/mpeg/audio/mod.rs") + tuple(_AAC + f for f in ("common.rs", "window.rs", "ics/gain.rs", "ics/ltp.rs", "ics/pulse.rs", "ics/tns.rs")),
+    _CORE + "io/bit.rs": ("IO", "tests/rust/small_rng.rs"),
+    _CORE + "checksum/md5.rs": ("IO",),
+    _CORE + "checksum/crc32.rs": ("IO",),
+    _CORE + "util.rs": (),
+    _CORE + "audio/conv.rs": (_CORE + "util.rs", _CORE + "audio/sample.rs"),
+    _CORE + "units.rs": (_CORE + "errors.rs",),
+    _CORE + "packet.rs": (_CORE + "errors.rs", _CORE + "units.rs"),
+    _CORE + "io/buf_reader.rs": ("IO",),
+    _CORE + "io/media_source_stream.rs": ("IO",),
+    _CORE + "audio/util.rs": (),
+    _CORE + "formats/mod.rs": ("IO",),
+    _CORE + "formats/util.rs": ("IO",),
+    "symphonia-common/src/xiph/audio/vorbis/mod.rs": ("IO",),
+}
+
+
+def reference_test_functions(root=REF):
+    """{file relative to the reference tree: [names of its `#[test]` functions, in source order]}, read off the parsed items (the parser
+    keeps an item's attributes), wherever in the file's modules they stand"""
+    found = {}
+
+    def walk(items, out):
+        for it in items:
+            if it[0] == "fn" and any(a.strip() == "test" for a in it[7]):
+                out.append((it[1], any(a.split()[0] == "should_panic" for a in it[7])))
+            elif it[0] == "mod":
+                walk(it[2], out)
+
+    for path in sorted(root.rglob("*.rs")):
+        src = path.read_text()
+        if "#[test]" not in src:
+            continue
+        out = []
+        walk(P.parse_source(src, str(path)), out)
+        if out:
+            found[str(path.relative_to(root))] = out
+    return found
+
+
+def apply_mutation(text, m):
+    """`text` of the file m["file"] with one token changed (tests/golden/reference_test_mutations.json).  The table holds positions and
+    tokens only; the sha256 makes a reference tree whose lines have moved fail here instead of changing something else."""
+    import hashlib
+    assert hashlib.sha256(text.encode()).hexdigest() == m["sha256"], "%s is not the text the mutation table was written for" % m["file"]
+    lines = text.split("\n")
+    line = lines[m["line"] - 1]
+    parts = line.split(m["old"])
+    assert len(parts) > m["occurrence"], "line %d of %s holds %r fewer than %d times" % (m["line"], m["file"], m["old"], m["occurrence"])
+    k = m["occurrence"]
+    lines[m["line"] - 1] = m["old"].join(parts[:k]) + m["new"] + m["old"].join(parts[k:])
+    return "\n".join(lines)
+
+
+def reference_test_interp(rel, mutation=None, edit=None):
+    """An interpreter holding what REFERENCE_TEST_SIBLINGS lists for `rel`, then `rel` itself: call `tests::<fn>` on it.
+    `mutation` (a row of the mutation table) changes one token of the one file it names; `edit(text)` rewrites `rel`'s text in memory."""
+    it = Interp()
+    todo = []
+    for s in REFERENCE_TEST_SIBLINGS[rel] + (rel,):
+        if s == "IO":
+            todo += [_CORE + f for f in CORE_IO if _CORE + f != rel] + ([_CORE + "io/bit.rs"] if rel != _CORE + "io/bit.rs" else [])
+        else:
+            todo.append(s)
+    hit = False
+    for f in todo:
+        if f.startswith("tests/"):
+            it.load_file(ROOT / f)
+            continue
+        text = (REF / f).read_text()
+        if mutation is not None and mutation["file"] == f:
+            text, hit = apply_mutation(text, mutation), True
+        if f == rel and edit is not None:
+            text = edit(text)
+        if f.endswith("io/bit.rs"):
+            text = expand_vlc_entries(text)
+        it.load_source(text, f)
+    assert mutation is None or hit, "%s is not among the files loaded for %s" % (mutation["file"], rel)
+    bad = it.globals.get("__unparsed__")
+    assert not bad, bad
+    return it
+
+
 _SHARED_STATICS = {}  # the reference's lazily built tables (VLC codebooks, pow43, windows): built once per process and source text
 
 

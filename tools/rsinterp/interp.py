@@ -50,6 +50,10 @@ class InterpError(Exception):
     pass
 
 
+class NoMethod(InterpError):
+    """no built-in (inherent) method of that name on a primitive: a trait the loaded text implements for it may have one"""
+
+
 class BreakEx(Exception):
     def __init__(self, label, value):
         self.label, self.value = label, value
@@ -567,6 +571,7 @@ class Interp:
         self.shared_statics = None  # optional dict shared between interpreters: (sha1 of the source text, name) -> value of a `static`
         self.src_hash = {}     # file name -> sha1 of its text
         self.alt_methods = {}  # (type name, method name) -> [fn items] when an inherent and a trait method share a name
+        self.overloads = {}    # (type name, method name) -> [fn items] of `impl Trait<A> for T`, `impl Trait<B> for T`, ...
         self.macros = {}       # macro_rules
         self.trait_impls = {}  # type name -> [trait names it implements]
         self.traits = set()    # trait names
@@ -623,6 +628,11 @@ class Interp:
                             # `<Dsp as SynthBackend>::synth`): rustc tells them apart by the path / the receiver's static type, which
                             # are not tracked here; the two that occur differ in their parameter count, and call_fn picks by that
                             self.alt_methods.setdefault((tname, sub[1]), [old]).append(sub)
+                        elif isinstance(old, tuple) and old[0] == 'fn' and old is not sub and it[2] is not None and it[2][0] == 'tpath' and it[2][2]:
+                            # one generic trait implemented several times for one type (`impl From<i16> for i24`, `impl From<i32>
+                            # for i24`; `impl FromSample<F> for u8` for ten F): rustc selects the impl by the argument's type, and so
+                            # does call_fn (pick_overload)
+                            self.overloads.setdefault((tname, sub[1]), [old]).append(sub)
                         d[sub[1]] = sub
                     elif sub[0] in ('const', 'static'):
                         d[sub[1]] = Lazy(sub, self, Env(self_type=tname, uses=sub[5].uses))
@@ -854,7 +864,16 @@ class Interp:
                     raise InterpError('integer literal where %s is expected' % name)
                 return v
             if name in INT_BITS:
+                if isinstance(v, TryInto) and isinstance(v.v, Int):  # the declared type names the target `try_into()` left open
+                    if not in_range(v.v.v, name):
+                        raise TryIntoOutOfRange(name)
+                    return Int(v.v.v, name)
                 if isinstance(v, Int) and v.t is None:
+                    if v.v < 0 and name[0] == 'u' and v.v >= -(1 << INT_BITS[name]):
+                        # rustc rejects a negative literal for an unsigned type, so an untyped negative that reaches one is the
+                        # complement of untyped literals (`!((1 << idx) - 1)` returning u8): `!` in that type, which inference
+                        # would have given the literals, is the two's-complement image
+                        return Int(wrap_int(v.v, name), name)
                     if not in_range(v.v, name):
                         raise InterpError('literal %d out of range for %s' % (v.v, name))
                     return Int(v.v, name)
@@ -1035,12 +1054,22 @@ class Interp:
         if isinstance(f, tuple):
             if f[0] == 'ctor':
                 sd = self.types[f[1]]
+                if len(args) == len(sd[3]):  # a tuple struct's constructor is a function of its declared field types
+                    return Struct(f[1], {str(i): self.coerce(a, ty, env or Env()) for i, (a, (_, ty)) in enumerate(zip(args, sd[3]))})
                 return Struct(f[1], {str(i): a for i, a in enumerate(args)})
             if f[0] == 'variant_ctor':
                 return Enum(f[1], f[2], {str(i): a for i, a in enumerate(args)})
+            if f[0] == 'type' and f[1] in self.types and self.types[f[1]][0] == 'struct' and self.types[f[1]][2] == 'tuple':
+                sd = self.types[f[1]]  # `Self(..)` in an impl of a tuple struct
+                if len(args) != len(sd[3]):
+                    raise InterpError('%s(..) takes %d fields' % (f[1], len(sd[3])))
+                return Struct(f[1], {str(i): self.coerce(a, ty, env or Env()) for i, (a, (_, ty)) in enumerate(zip(args, sd[3]))})
         raise InterpError('not callable: %r' % (f,))
 
     def call_fn(self, item, args, gargs=None, self_type=None, caller_env=None, self_val=None):
+        cands = self.overloads.get((self_type, item[1]))
+        if cands is not None and item in cands:
+            item = self.pick_overload(cands, args, item[4] is not None and self_val is None)
         _, name, gen, params, self_kind, ret, body, attrs, parser = item
         env = Env(self_type=self_type, uses=parser.uses)
         if gen:
@@ -1085,6 +1114,39 @@ class Interp:
         if ret is not None:
             v = self.coerce(v, ret, env)
         return v
+
+    @staticmethod
+    def static_type_of(v):
+        """the name of a value's Rust type where the value carries it (None for an untyped literal)"""
+        v = deref(v)
+        if isinstance(v, Int):
+            return v.t
+        if isinstance(v, (bool, np.bool_)):
+            return 'bool'
+        if isinstance(v, F32):
+            return 'f32'
+        if isinstance(v, float):
+            return 'f64'
+        if isinstance(v, Struct):
+            return v.name
+        if isinstance(v, Enum):
+            return v.enum
+        return None
+
+    def pick_overload(self, cands, args, self_in_args):
+        """among the impls of one generic trait for one type, the one whose first non-self parameter has the argument's type"""
+        if len(args) <= int(self_in_args):
+            raise InterpError('cannot select among the impls of %s without an argument' % cands[0][1])
+        t = self.static_type_of(args[int(self_in_args)])
+        if t is None:  # a literal several impls could take: its type falls back to i32 / f64 (Rust Reference, "Literal expressions")
+            v = deref(args[int(self_in_args)])
+            t = 'i32' if isinstance(v, Int) else 'f64' if isinstance(v, ULit) else None
+        if t is None:
+            raise InterpError('cannot select among the impls of %s for %r' % (cands[0][1], args[int(self_in_args)]))
+        hits = [c for c in cands if c[3] and self.type_name(c[3][0][1]) == t]
+        if len(hits) != 1:
+            raise InterpError('%d impls of %s take a %s' % (len(hits), cands[0][1], t))
+        return hits[0]
 
     # ---------------------------------------------------------------- patterns
     def match(self, pat, v, env, bind):
@@ -1379,11 +1441,10 @@ class Interp:
         return e[1]
 
     def e_str(self, e, env):
-        s = e[1]
-        if s.startswith('b"'):  # a byte-string literal is a `&[u8; N]`
-            raw = s[2:-1].encode('ascii').decode('unicode_escape').encode('latin-1')
-            return Arr([Int(b, 'u8') for b in raw], False)
-        return s
+        is_bytes, text = P.string_literal_value(e[1])
+        if is_bytes:  # a byte-string literal is a `&[u8; N]`
+            return Arr([Int(ord(c), 'u8') for c in text], False)
+        return text
 
     def e_char(self, e, env):
         return Int(e[1], 'u8' if e[2] else 'char')
@@ -1525,6 +1586,25 @@ class Interp:
               'bitxor': lambda p, q: p ^ q}[method]
         return Struct('Wrapping', {'0': Int(wrap_int(op(x.v, y.v), t), t)})
 
+    def derived_cmp(self, a, b):
+        """-1 / 0 / 1 by `#[derive(PartialOrd)]` on a struct: lexicographic over the fields in the order they are declared (std::cmp,
+        "Derivable").  A type that orders itself by a hand-written `partial_cmp` is refused (InterpError), not guessed at."""
+        item = self.types.get(a.name)
+        if item is None or item[0] != 'struct' or not any(x.startswith('derive') and 'PartialOrd' in x for x in item[4]) \
+                or 'partial_cmp' in self.impls.get(a.name, {}):
+            raise InterpError('ordering of %s is not derived' % a.name)
+        for fname, _ in item[3]:
+            x, y = deref(a.f[fname]), deref(b.f[fname])
+            if isinstance(x, Struct) and isinstance(y, Struct):
+                c = self.derived_cmp(x, y)
+                if c:
+                    return c
+            elif truth(self.binop('<', x, y)):
+                return -1
+            elif truth(self.binop('>', x, y)):
+                return 1
+        return 0
+
     BIN_TRAIT = {'+': 'add', '-': 'sub', '*': 'mul', '/': 'div', '%': 'rem', '<<': 'shl', '>>': 'shr', '&': 'bitand', '|': 'bitor', '^': 'bitxor'}
 
     def binop(self, op, a, b):
@@ -1573,6 +1653,9 @@ class Interp:
                 return values_equal(a, b)
             if op == '!=':
                 return not values_equal(a, b)
+            if op in ('<', '>', '<=', '>=') and tb is Struct and a.name == b.name:
+                c = self.derived_cmp(a, b)
+                return {'<': c < 0, '>': c > 0, '<=': c <= 0, '>=': c >= 0}[op]
         fa, fb = float_type_of(a), float_type_of(b)
         if fa is not None and fb is not None:
             if fa != fb:
@@ -1611,6 +1694,12 @@ class Interp:
         if isinstance(a, tuple) and isinstance(b, tuple) and op in ('<', '>', '<=', '>='):
             ka, kb = tuple(sort_key(x) for x in a), tuple(sort_key(x) for x in b)
             return {'<': ka < kb, '>': ka > kb, '<=': ka <= kb, '>=': ka >= kb}[op]
+        if isinstance(a, Enum) and isinstance(b, Enum) and a.enum == b.enum == 'Option' and op in ('<', '>', '<=', '>='):
+            # Option<T: PartialOrd>: None is less than any Some, two Somes compare by their contents (std::option, "Comparison operators")
+            if a.variant == 'Some' and b.variant == 'Some':
+                return self.binop(op, a.f['0'], b.f['0'])
+            ka, kb = a.variant == 'Some', b.variant == 'Some'
+            return {'<': ka < kb, '>': ka > kb, '<=': ka <= kb, '>=': ka >= kb}[op]
         raise InterpError('binary %s on %r and %r' % (op, a, b))
 
     def int_binop(self, op, a, b):
@@ -1647,12 +1736,9 @@ class Interp:
             if t is None:
                 return Int(r)
             return Int(wrap_int(r, t), t)
-        elif op == '&':
-            r = x & y
-        elif op == '|':
-            r = x | y
-        elif op == '^':
-            r = x ^ y
+        elif op in ('&', '|', '^'):  # cannot overflow; an untyped operand may be a complement (`x | !0`), negative until typed
+            r = x & y if op == '&' else x | y if op == '|' else x ^ y
+            return Int(r) if t is None else Int(wrap_int(r, t), t)
         elif op == '<':
             return x < y
         elif op == '>':
@@ -1986,7 +2072,10 @@ class Interp:
             if len(segs) >= 2:
                 head = segs[-2]
                 if head in FLOAT_TYPES or head in INT_BITS:
-                    r = self.prim_assoc(head, segs[-1], args)
+                    try:
+                        r = self.prim_assoc(head, segs[-1], args)
+                    except NoMethod:  # not std's: an associated function a loaded trait impl gives the primitive (`u8::from_sample`)
+                        r = NotImplemented
                     if r is not NotImplemented:
                         return r
             f = self.evr(('path', segs, gargs), env)
@@ -2071,6 +2160,26 @@ class Interp:
             return ext
         if head == 'consts' and len(segs) >= 3 and segs[-3] in FLOAT_TYPES:
             return self.prim_const(segs[-3], name)
+        if head == 'char' and name == 'REPLACEMENT_CHARACTER':
+            return Int(0xFFFD, 'char')
+        if head == 'char' and name == 'from':
+            return Builtin(lambda v: Int(deref(v).v, 'char'), 'char::from')
+        if head == 'char' and name == 'decode_utf16':  # Iterator<Item = Result<char, DecodeUtf16Error>>: an unpaired surrogate is an Err
+            def decode_utf16(units):
+                u = [deref(x).v for x in self.into_iter(units)]
+                out, i = [], 0
+                while i < len(u):
+                    c = u[i]
+                    i += 1
+                    if 0xD800 <= c < 0xDC00 and i < len(u) and 0xDC00 <= u[i] < 0xE000:
+                        out.append(ok(Int(0x10000 + ((c - 0xD800) << 10) + (u[i] - 0xDC00), 'char')))
+                        i += 1
+                    elif 0xD800 <= c < 0xE000:
+                        out.append(err(Struct('DecodeUtf16Error', {'code': Int(c, 'u16')})))
+                    else:
+                        out.append(ok(Int(c, 'char')))
+                return RIter(lst=out)
+            return Builtin(decode_utf16, 'char::decode_utf16')
         if head in FLOAT_TYPES or head in INT_BITS:
             if name in ('MAX', 'MIN', 'BITS', 'EPSILON', 'INFINITY', 'NEG_INFINITY', 'NAN', 'MIN_POSITIVE'):
                 return self.prim_const(head, name)
@@ -2130,6 +2239,18 @@ class Interp:
             return Builtin(rep, 'iter::repeat')
         if name == 'drop':
             return Builtin(lambda v: UNIT, 'drop')
+        if head == 'String' and name == 'new':
+            return Builtin(lambda: '', 'String::new')
+        if head == 'String' and name == 'from':
+            return Builtin(lambda v: deref(v), 'String::from')
+        if head in ('str', 'String') and name in ('from_utf8', 'from_utf8_lossy'):
+            def from_utf8(v, _lossy=name == 'from_utf8_lossy'):
+                raw = bytes(x.v for x in seq_list(deref(v)))
+                try:
+                    return raw.decode('utf-8', 'replace') if _lossy else ok(raw.decode('utf-8'))
+                except UnicodeDecodeError:
+                    return err(Struct('Utf8Error', {}))
+            return Builtin(from_utf8, head + '::' + name)
         return None
 
     # ---------------------------------------------------------------- macros
@@ -2196,8 +2317,14 @@ class Interp:
             key = id(e)
             node = self.node_cache.get(key)
             if node is None:
-                node = P.parse_tokens_as_expr(self.expand_macro(name, toks))
+                out = self.expand_macro(name, toks)
+                try:
+                    node = P.parse_tokens_as_expr(out)
+                except P.ParseError:  # an arm whose body is statements (`$a = ..; $a = ..;`): a block in the caller's scope
+                    node = P.parse_tokens_as_block(out)
                 self.node_cache[key] = node
+            if node[0] == 'block':
+                return self.ev_block(node, env)
             return self.ev(node, env)
         raise InterpError('macro %s! is not supported' % name)
 
@@ -2236,7 +2363,14 @@ class Interp:
                 self_val = copyval(base) if m[4] == 'value' else ObjPlace(base)
                 return self.call_fn(m, args, gargs, tname, env, self_val=self_val)
         args = [self.ev(a, env) for a in arg_es]
-        return self.builtin_method(base, name, args, recv, env, gargs)
+        try:
+            return self.builtin_method(base, name, args, recv, env, gargs)
+        except NoMethod:  # not an inherent method of the primitive: a trait method of the loaded text (`impl Sample for f32`)
+            tname = self.static_type_of(base)
+            m = self.impls.get(tname, {}).get(name) or (self.trait_default(tname, name) if tname else None)
+            if not (isinstance(m, tuple) and m[0] == 'fn'):
+                raise
+            return self.call_fn(m, args, gargs, tname, env, self_val=base)
 
     def trait_default(self, tname, name):
         """the default body of method `name` in a trait `tname` implements (or in one of that trait's supertraits)"""
@@ -2353,17 +2487,42 @@ class Interp:
             if name in ('unwrap', 'expect'):
                 return base.v
             if name == 'ok':
+                if isinstance(base.v, Int):  # whether it is Some depends on a target type only a later typed use names
+                    return PendingOk(base)
                 return some(base.v)
+        if tb is PendingOk:
+            if name == 'map':  # `x.try_into().ok().map(|v| T { field: v })`: the field's declared type is the target; out of range
+                try:           # there (coerce) means the conversion had failed, so the Option was None all along
+                    r = self.call_value(args[0], [base.t])
+                except TryIntoOutOfRange:
+                    return NONE
+                # a field whose declared type is not a named primitive (`Jump { index: E::IndexType }`, an associated type the
+                # interpreter does not track) leaves the target open: the value goes on unconverted, as Some
+                if r is base.t:
+                    r = base.t.v
+                elif isinstance(r, (Struct, Enum)) and r.f:
+                    for k, x in r.f.items():
+                        if x is base.t:
+                            r.f[k] = base.t.v
+                return some(r)
+            raise InterpError('cannot infer the target type of try_into().ok().%s()' % name)
         if tb is str:
-            if name in ('len',):
-                return Int(len(base), 'usize')
+            if name in ('len',):  # the length of a `str` is its UTF-8 length in bytes
+                return Int(len(base.encode('utf-8')), 'usize')
+            if name == 'is_empty':
+                return not base
+            if name in ('as_bytes', 'bytes', 'into_bytes'):
+                data = Arr([Int(b, 'u8') for b in base.encode('utf-8')], name == 'into_bytes')
+                return self.into_iter(data) if name == 'bytes' else data
+            if name == 'chars':
+                return RIter(lst=[Int(ord(c), 'char') for c in base])
             return base
         if tb is Closure or tb is FnRef:
             if name in ('clone', 'borrow'):
                 return base
         if tb is Uninit:
             raise InterpError('use of a Default::default() placeholder (method %s)' % name)
-        raise InterpError('no method %s on %r' % (name, base))
+        raise NoMethod('no method %s on %r' % (name, base))
 
     def int_method(self, x, name, args):
         t = x.t
@@ -2520,7 +2679,7 @@ class Interp:
             return Enum('Ordering', 'Less' if x.v < o else 'Greater' if x.v > o else 'Equal')
         if name == 'is_ascii_digit':
             return 48 <= x.v <= 57
-        raise InterpError('no int method %s' % name)
+        raise NoMethod('no int method %s' % name)
 
     def float_method(self, x, name, args):
         is32 = not isinstance(x, float)
@@ -2630,6 +2789,8 @@ class Interp:
             if name == 'recip':
                 return F32(1.0) / x if is32 else _fdiv(1.0, x)
             if name == 'signum':
+                if x != x:  # std: NaN if the number is NaN
+                    return x
                 return np.copysign(F32(1.0), x) if is32 else math.copysign(1.0, x)
             if name == 'copysign':
                 return np.copysign(x, a[0]) if is32 else math.copysign(x, a[0])
@@ -2660,7 +2821,7 @@ class Interp:
             if name in ('lt', 'le', 'gt', 'ge', 'eq', 'ne'):
                 o = a[0]
                 return {'lt': x < o, 'le': x <= o, 'gt': x > o, 'ge': x >= o, 'eq': x == o, 'ne': x != o}[name]
-        raise InterpError('no float method %s' % name)
+        raise NoMethod('no float method %s' % name)
 
     def seq_method(self, v, name, args, recv, env, gargs):
         a, o, n = seq_view(v)
@@ -2682,6 +2843,22 @@ class Interp:
             return Arr([copyval(x) for x in a[o:o + n]], name != 'clone' or (isinstance(v, Arr) and v.vec) or isinstance(v, Slice))
         if name == 'try_into':
             return TryInto(recv if isinstance(recv, Place) else v)  # a reference stays a reference
+        if name == 'partition_point':  # a binary search, as std's: the first index whose element fails the predicate
+            lo, hi = 0, n
+            while lo < hi:
+                mid = lo + (hi - lo) // 2
+                if truth(self.call_value(args[0], [a[o + mid]])):
+                    lo = mid + 1
+                else:
+                    hi = mid
+            return Int(lo, 'usize')
+        if name in ('first_chunk', 'last_chunk'):  # `slice.first_chunk::<N>()`: Option<&[T; N]>
+            if not gargs:
+                raise InterpError('%s needs its length named (::<N>)' % name)
+            k = deref(self.ev(gargs[0][1], env)) if gargs[0][0] == 'gconst' else Int(int(self.type_name(gargs[0][1])), 'usize')
+            if k.v > n:
+                return NONE
+            return some(Slice(a, o if name == 'first_chunk' else o + n - k.v, k.v))
         if name == 'fill':
             val = args[0]
             if n and isinstance(val, (ULit, Int)):
@@ -2977,6 +3154,11 @@ class Interp:
                 return some(x)
             l.clear()
             return NONE
+        if name == 'as_slice':  # slice::Iter::as_slice: what has not been yielded yet
+            rest = list(it.tolist())
+            return Slice(rest, 0, len(rest))
+        if name == 'collect' and gargs and gargs[0][0] == 'gtype' and self.type_name(gargs[0][1]) == 'String':
+            return ''.join(x if isinstance(x, str) else chr(x.v) for x in (deref(y) for y in it))
         if name == 'collect':
             out = []
             for x in it:  # an iterator of `Result`s collects into `Result<Vec<_>, E>` (the only use in the texts run here): the
@@ -3046,7 +3228,7 @@ class Interp:
             return RIter(g())
         if name == 'inspect':
             return it
-        raise InterpError('no iterator method %s' % name)
+        raise NoMethod('no iterator method %s' % name)
 
     def enum_method(self, v, name, args, env):
         if v.enum in ('Option', 'Result'):
@@ -3107,6 +3289,18 @@ class Interp:
             v.variant, v.f = 'None', None
             return old
         raise InterpError('no method %s on %r' % (name, v))
+
+
+class TryIntoOutOfRange(Exception):
+    pass
+
+
+class PendingOk:
+    """`int.try_into().ok()` before its target type is known (see builtin_method)"""
+    __slots__ = ('t',)
+
+    def __init__(self, t):
+        self.t = t
 
 
 class TryInto:

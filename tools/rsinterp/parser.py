@@ -52,6 +52,46 @@ def lex(src):
     return toks
 
 
+STR_ESCAPES = {'n': '\n', 't': '\t', 'r': '\r', '0': '\0', '\\': '\\', "'": "'", '"': '"'}
+
+
+def string_literal_value(tok):
+    """(is a byte string, the characters) of a string-literal token, by the Rust Reference's "String literals" / "Byte string
+    literals": quote escapes, \\n \\r \\t \\0 \\\\, \\xHH, \\u{H..}; a backslash at the end of a line drops the line break AND all the white space
+    (space, tab, LF, CR) that follows it; a raw string (r"..", r#".."#) has no escapes at all."""
+    is_bytes = tok.startswith('b')
+    if is_bytes:
+        tok = tok[1:]
+    if tok.startswith('r'):
+        n = tok.index('"')  # = 1 + the number of '#'
+        return is_bytes, tok[n + 1:len(tok) - n]
+    body, out, i = tok[1:-1], [], 0
+    while i < len(body):
+        c = body[i]
+        if c != '\\':
+            out.append(c)
+            i += 1
+            continue
+        c = body[i + 1]
+        if c == 'x':
+            out.append(chr(int(body[i + 2:i + 4], 16)))
+            i += 4
+        elif c == 'u':
+            j = body.index('}', i)
+            out.append(chr(int(body[i + 3:j].replace('_', ''), 16)))
+            i = j + 1
+        elif c == '\n' or (c == '\r' and body[i + 2:i + 3] == '\n'):
+            i += 2
+            while i < len(body) and body[i] in ' \t\n\r':
+                i += 1
+        elif c in STR_ESCAPES:
+            out.append(STR_ESCAPES[c])
+            i += 2
+        else:
+            raise ParseError('unknown escape \\%s in a string literal' % c)
+    return is_bytes, ''.join(out)
+
+
 ASSIGN_OPS = {'=', '+=', '-=', '*=', '/=', '%=', '^=', '&=', '|=', '<<=', '>>='}
 BIN_PREC = {
     '*': 11, '/': 11, '%': 11, '+': 10, '-': 10, '<<': 9, '>>': 9, '&': 8, '^': 7, '|': 6,
@@ -1351,6 +1391,16 @@ def parse_tokens_as_expr(toks, fname='<macro>'):
     if p.cur.k != 'eof':
         p.err('trailing tokens after expression')
     return e
+
+
+def parse_tokens_as_block(toks, fname='<macro>'):
+    """a macro expansion in statement position: `a = ..; b = ..;` (any number of statements, an optional tail expression)"""
+    line = toks[-1].line if toks else 0
+    p = Parser(list(toks) + [Tok('punct', '}', line), Tok('eof', '', line)], fname)
+    blk = p.block_body()
+    if p.cur.k != 'eof':
+        p.err('trailing tokens after the statements of a macro expansion')
+    return blk
 
 
 def parse_tokens_as_items(toks, fname='<macro>'):
