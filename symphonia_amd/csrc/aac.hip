@@ -143,6 +143,16 @@ __device__ __forceinline__ void st_slot(float *frame, int m2, const float (&v)[8
 // Wave 0's predecessor is wave 3 of the step before: that slot is a double-buffered 4 KiB carry buffer of its own (the
 // other three live in the owners' FFT work areas, which the next transform overwrites -- hence the second barrier).
 // A segment starts with a step in which only wave 3 runs: the halo frame (or the chain's incoming delay) fills the carry.
+//
+// The walk is three pieces of the same step: the HALO step (wave 3 alone, phase 1 only, no barrier: the carry it fills is read
+// behind the first barrier of step 0), the FULL steps of the main loop (four frames, nothing conditional but the window
+// sequence) and one RAGGED last step when the segment's length is not a multiple of four.  What the main loop is shaped for:
+// gfx950 counts vector loads and stores with ONE in-order counter, so a wait for the prefetched lines also waits for every
+// store issued in front of it that the compiler cannot prove to lie BEHIND them.  In a full step the prefetch is unconditional
+// (past the segment's end a wavefront re-reads the frame it is working on: inside the chain, never used), every long arm
+// issues exactly its four PCM stores behind it, and the prefetched registers are claimed in straight-line code right behind
+// those stores (settle_prefetch): the wait is vmcnt(4) -- for the lines, with the four stores still in flight -- and the loop
+// header needs none.  (The chain's outgoing delay line is a conditional store behind that point.)
 constexpr int kSlotOff = kShortRowsEnd;  // floats: the slot lies behind the eight short-window rows, inside the FFT work area
 static_assert(kSlotOff + 1024 <= kWaveLds, "delay slot must fit the per-wave LDS behind the short-window rows");
 
@@ -159,6 +169,20 @@ static_assert(kSlotOff + 1024 <= kWaveLds, "delay slot must fit the per-wave LDS
 // the plain instantiation, launched over all chains: a workgroup whose chain is in `chain` (the index the expansion fills)
 // returns at once.  The lane-index trick of the Vorbis big-block kernels (an empty asm per step) keeps the pair instantiation
 // inside 256 registers.
+enum : int { kStepHalo = 0, kStepFull = 1, kStepRagged = 2 };
+template <int V> using step_kind = std::integral_constant<int, V>;
+
+// Claims the prefetched frame where it is called: the registers are valid from here on, so this is where the compiler waits for
+// the loads -- and for nothing that was issued behind them.
+__device__ __forceinline__ void settle_prefetch(const float2 (&line)[8]) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __builtin_amdgcn_sched_barrier(0);  // (the stores in front of this point are ISSUED in front of it)
+    // (read, not redefined: no copies; one statement: one wait)
+    asm volatile("" : : "v"(line[0].x), "v"(line[0].y), "v"(line[1].x), "v"(line[1].y), "v"(line[2].x), "v"(line[2].y), "v"(line[3].x), "v"(line[3].y),
+                        "v"(line[4].x), "v"(line[4].y), "v"(line[5].x), "v"(line[5].y), "v"(line[6].x), "v"(line[6].y), "v"(line[7].x), "v"(line[7].y));
+#endif
+}
+
 struct AacJsArgs {
     const int2 *chain;                  // per chain: .x = the partner chain (-1: not part of a pair) -- the plain kernel's skip list
     const int32_t *pair_chains;         // [pair][2]: the left and the right chain
@@ -166,6 +190,10 @@ struct AacJsArgs {
     AacBandMaps maps;                   // line / 4 -> scale-factor band (long / short windows)
     unsigned n_chains;                  // chains of the batch: the bound of pair_chains[]
 };
+
+#if SYM_AAC_QUAD == 2
+#include "experiments/aac_quad_probe.h"  // development only: the shader-cycle split of a step (results are wrong by construction)
+#endif
 
 template <bool JS>
 __global__ __launch_bounds__(256, SYM_AAC_MIN_WAVES) void aac_synth_quad_kernel(
@@ -188,7 +216,9 @@ __global__ __launch_bounds__(256, SYM_AAC_MIN_WAVES) void aac_synth_quad_kernel(
             tabs[kTabSineShort + i] = tb.aac_sine_short[i];
         }
     }
-    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+    // the wave index as a SCALAR: the frame a wavefront owns, its addresses and (with the side byte, below) every decision of a step
+    // are then wave-uniform to the compiler too -- scalar branches of which one arm runs, not exec-masked regions
+    const int lane = (int)threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
     float *ldsf = wave_lds[wave];
     c32 *lds = reinterpret_cast<c32 *>(ldsf);
     const c32 *tw = reinterpret_cast<const c32 *>(tabs + kTabTw);
@@ -200,13 +230,14 @@ __global__ __launch_bounds__(256, SYM_AAC_MIN_WAVES) void aac_synth_quad_kernel(
     }
     const long t_begin = (long)seg * seg_steps * 4;
     const long t_end = t_begin + (long)seg_steps * 4 < (long)frames_per_chain ? t_begin + (long)seg_steps * 4 : (long)frames_per_chain;
-    const long n_steps = (t_end - t_begin + 3) / 4;
+    if (t_end <= t_begin) return;  // (no segment of a launch is empty)
     const size_t chain_base0 = (size_t)chain * frames_per_chain, chain_base1 = (size_t)chain1 * frames_per_chain;
     LaneTables lt;
     load_lane_tables(tb, lane, lt);
 
-    // the carry in front of the segment: the caller's delay line at a chain's start, else what the halo frame leaves (step -1)
-    if (t_begin == 0 && wave == 3) {
+    // the carry in front of the segment: the caller's delay line at a chain's start, else what the halo frame leaves (the halo step)
+    const bool has_halo = t_begin > 0;
+    if (!has_halo && wave == 3) {
 #pragma unroll
         for (int ch = 0; ch < CH; ++ch) {
             const float4 *src = reinterpret_cast<const float4 *>(delay_in + (size_t)(ch ? chain1 : chain) * 1024);
@@ -214,11 +245,11 @@ __global__ __launch_bounds__(256, SYM_AAC_MIN_WAVES) void aac_synth_quad_kernel(
             for (int q = 0; q < 4; ++q) reinterpret_cast<float4 *>(carry[ch][1])[lane + 64 * q] = src[lane + 64 * q];
         }
     }
-    // `line` always holds the lines of frame t_loaded: the halo frame for wave 3 of a later segment, else the frame of step 0
-    long t_loaded = (wave == 3 && t_begin > 0) ? t_begin - 1 : t_begin + wave;
+    // the first frame a wavefront transforms: the halo frame for wave 3 of a later segment, else its frame of step 0
+    const long t_first = (wave == 3 && has_halo) ? t_begin - 1 : t_begin + wave;
     float2 line[8];
     unsigned sb_next = 0;
-    // JS: channel 1's lines and side byte, and the stereo map of frame t_loaded
+    // JS: channel 1's lines and side byte, and the stereo map of the frame in `line`
     float2 line1[8];
     // The frame's 644-byte stereo descriptor travels with the lines as three dwords per lane (161 in all) and is laid down in the
     // wavefront's LDS area at the top of the step (the area is idle there), where the lanes look up mode[] and scale[] of their
@@ -245,14 +276,13 @@ __global__ __launch_bounds__(256, SYM_AAC_MIN_WAVES) void aac_synth_quad_kernel(
         for (int s = 0; s < 8; ++s) sfb_long[s >> 2] |= (uint32_t)js.maps.long4[(lane >> 1) + 32 * s] << (8 * (s & 3));
         sfb_short = js.maps.short4[(lane >> 1) & 31];
     }
-    if (t_loaded < t_end) {
-        const float2 *src = reinterpret_cast<const float2 *>(coeffs + (chain_base0 + (size_t)t_loaded) * 1024);
+    if (t_first < t_end) {
+        const float2 *src = reinterpret_cast<const float2 *>(coeffs + (chain_base0 + (size_t)t_first) * 1024);
 #pragma unroll
         for (int s = 0; s < 8; ++s) line[s] = ld_line(src + lane + 64 * s);
-        sb_next = side[chain_base0 + (size_t)t_loaded];
-        fetch1(t_loaded, lane);
-    } else {
-        t_loaded = -100;
+        sb_next = side[chain_base0 + (size_t)t_first];
+        fetch1(t_first, lane);
+    } else {  // (a wavefront without a frame: a segment shorter than four frames)
 #pragma unroll
         for (int s = 0; s < 8; ++s) line[s] = make_float2(0.0f, 0.0f);
         if constexpr (JS) {
@@ -262,18 +292,20 @@ __global__ __launch_bounds__(256, SYM_AAC_MIN_WAVES) void aac_synth_quad_kernel(
     }
     __syncthreads();  // tables and the carry are in place
 
-    long t = t_begin - 4 + wave;  // this wavefront's frame of step i
     const int lane_of_wave = lane;
-    for (long i = -1; i < n_steps; ++i, t += 4) {
+    // One step: wave j's frame `t` of step i.  KIND (compile time): the halo step (phase 1 alone, no barrier), a full step of the main
+    // loop (`active` is the literal true), the ragged last step (`active`: the wavefront has a frame; nothing is prefetched).
+    auto step = [&](auto kind_c, int i, long t, bool active) __attribute__((always_inline)) {
+        constexpr int KIND = decltype(kind_c)::value;
         int lane = lane_of_wave;
         if constexpr (JS) {
 #if defined(__HIP_DEVICE_COMPILE__)
             asm volatile("" : "+v"(lane));  // (what the step derives from the lane index is recomputed per step, not held in ~70 registers)
 #endif
         }
-        const bool active = t == t_loaded;  // (step -1: only a wave 3 with a halo frame)
-        const bool emit = i >= 0;
-        const unsigned sb0 = sb_next, sb1 = sb1_next;
+        // the side byte is the same for the whole wavefront: as a scalar the window-sequence decisions are uniform branches
+        const unsigned sb0 = (unsigned)__builtin_amdgcn_readfirstlane((int)sb_next);
+        const unsigned sb1 = JS ? (unsigned)__builtin_amdgcn_readfirstlane((int)sb1_next) : 0u;
         if constexpr (JS) {
             if (active) {  // both channels of the frame, decoded in registers (cpe.rs:110-157)
                 uint32_t *dl = reinterpret_cast<uint32_t *>(ldsf);  // the descriptor: num_windows | max_sfb << 8 | .. ; mode[128]; scale[128]
@@ -303,7 +335,11 @@ __global__ __launch_bounds__(256, SYM_AAC_MIN_WAVES) void aac_synth_quad_kernel(
                 wave_sync();  // (the area is the transform's again)
             }
         }
-        const long tn = t < t_begin ? t_begin + 3 : t + 4;  // (after the halo frame t_begin - 1 wave 3 continues with t_begin + 3)
+        // The frame this wavefront prefetches during the step.  Halo step: wave 3 continues with t_begin + 3, if the segment has it.
+        // Full step: t + 4 -- past the segment's end the frame being transformed once more (a valid address, never used), so that
+        // the number of loads in flight does not depend on where the segment ends.
+        const long tn = KIND == kStepHalo ? t_begin + 3 : (t + 4 < t_end ? t + 4 : t);
+        const bool fetch = KIND == kStepFull || (KIND == kStepHalo && tn < t_end);
 #pragma unroll 1
         for (int ch = 0; ch < CH; ++ch) {
         if constexpr (JS) {
@@ -316,11 +352,59 @@ __global__ __launch_bounds__(256, SYM_AAC_MIN_WAVES) void aac_synth_quad_kernel(
         const int seq = (int)(sb & 3u);
         const int shape = (int)((sb >> 2) & 1u), prev_shape = (int)((sb >> 3) & 1u);
         float *my_slot = wave == 3 ? carry[ch][i & 1] : ldsf + kSlotOff;
-        const float *prev_slot = wave == 0 ? carry[ch][(i + 1) & 1] : wave_lds[wave - 1] + kSlotOff;
+        float *prev_slot = wave == 0 ? carry[ch][(i + 1) & 1] : wave_lds[wave > 0 ? wave - 1 : 0] + kSlotOff;
         float xw[2][8];  // long frames: first half of the IMDCT output times its window, waiting for the predecessor's delay
         auto ln_at = [&](int s) -> float2 {
             if constexpr (JS) return ch ? line1[s] : line[s];
             else return line[s];
+        };
+        // the window and delay half of a long frame, one arm per window sequence: ONLY_LONG carries none of the LONG_START / LONG_STOP
+        // special cases
+        auto long_tail = [&](auto seq_c) __attribute__((always_inline)) {
+            constexpr int SEQ = decltype(seq_c)::value;
+            const float *wprev = tabs + (prev_shape ? kTabKbd : kTabSine);  // prev_long_win (dsp.rs:71-74)
+            const float *wcur = tabs + (shape ? kTabKbd : kTabSine);        // long_win (dsp.rs:66-69)
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int m2 = lane + 64 * h;
+                float x[8], x2[8];
+                post_slot(lds, tw, m2, x, x2);
+                float wo[8];
+                if constexpr (SEQ == LONG_STOP) {
+                    const float *psw = tabs + (prev_shape ? kTabKbdShort : kTabSineShort);
+                    stop_window4(psw, 4 * m2, wo);
+                    stop_window4(psw, 1020 - 4 * m2, wo + 4);
+                } else {
+                    load_slot(wprev, m2, wo);
+                }
+#pragma unroll
+                for (int q = 0; q < 8; ++q) xw[h][q] = x[q] * wo[q];
+                // the delay this frame leaves (dsp.rs:132-157): pcm[1024 + j] * long_win[1023 - j], a short-window slope,
+                // or literal zero
+                float wd[8], nd[8];
+                if constexpr (SEQ == LONG_START) {
+                    const float *sw = tabs + (shape ? kTabKbdShort : kTabSineShort);
+                    start_window4(sw, 4 * m2, wd);
+                    start_window4(sw, 1020 - 4 * m2, wd + 4);
+                } else {
+                    float wr[8];
+                    if (SEQ == ONLY_LONG && shape == prev_shape) {  // the same table: the values just read (a stream that keeps its window shape)
+#pragma unroll
+                        for (int q = 0; q < 8; ++q) wr[q] = wo[q];
+                    } else {
+                        load_slot(wcur, m2, wr);
+                    }
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) wd[q] = wr[7 - q];
+                }
+#pragma unroll
+                for (int q = 0; q < 8; ++q) {
+                    const int j = q < 4 ? 4 * m2 + q : 1020 - 4 * m2 + (q - 4);
+                    const float v = x2[q] * wd[q];
+                    nd[q] = (SEQ == LONG_START && j >= kP1) ? 0.0f : v;
+                }
+                store_slot(my_slot, m2, nd);
+            }
         };
 
         // ---------------- phase 1: transform this wavefront's frame, publish the delay line it leaves behind
@@ -345,7 +429,7 @@ __global__ __launch_bounds__(256, SYM_AAC_MIN_WAVES) void aac_synth_quad_kernel(
             // left channel's transform, the right channel's and the descriptor during the right channel's -- `line1` holds the frame
             // being decoded until then; requesting all of it during the left channel's transform, through a second register set,
             // measured slower: 0.283 against 0.257 ms)
-            if (tn < t_end) {
+            if (fetch) {
                 if (ch == 0) {
                     sb_next = side[chain_base0 + (size_t)tn];
                     const float2 *src = reinterpret_cast<const float2 *>(coeffs + (chain_base0 + (size_t)tn) * 1024);
@@ -356,44 +440,9 @@ __global__ __launch_bounds__(256, SYM_AAC_MIN_WAVES) void aac_synth_quad_kernel(
             }
             if (seq != EIGHT_SHORT) {
                 fft512_wave(z, lane, lds, lt);
-                const float *wprev = tabs + (prev_shape ? kTabKbd : kTabSine);  // prev_long_win (dsp.rs:71-74)
-                const float *wcur = tabs + (shape ? kTabKbd : kTabSine);        // long_win (dsp.rs:66-69)
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const int m2 = lane + 64 * h;
-                    float x[8], x2[8];
-                    post_slot(lds, tw, m2, x, x2);
-                    float wo[8];
-                    if (seq == LONG_STOP) {
-                        const float *psw = tabs + (prev_shape ? kTabKbdShort : kTabSineShort);
-                        stop_window4(psw, 4 * m2, wo);
-                        stop_window4(psw, 1020 - 4 * m2, wo + 4);
-                    } else {
-                        load_slot(wprev, m2, wo);
-                    }
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) xw[h][q] = x[q] * wo[q];
-                    // the delay this frame leaves (dsp.rs:132-157): pcm[1024 + j] * long_win[1023 - j], a short-window slope,
-                    // or literal zero
-                    float wd[8], nd[8];
-                    if (seq == LONG_START) {
-                        const float *sw = tabs + (shape ? kTabKbdShort : kTabSineShort);
-                        start_window4(sw, 4 * m2, wd);
-                        start_window4(sw, 1020 - 4 * m2, wd + 4);
-                    } else {
-                        float wr[8];
-                        load_slot(wcur, m2, wr);
-#pragma unroll
-                        for (int q = 0; q < 8; ++q) wd[q] = wr[7 - q];
-                    }
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) {
-                        const int j = q < 4 ? 4 * m2 + q : 1020 - 4 * m2 + (q - 4);
-                        const float v = x2[q] * wd[q];
-                        nd[q] = (seq == LONG_START && j >= kP1) ? 0.0f : v;
-                    }
-                    store_slot(my_slot, m2, nd);
-                }
+                if (seq == ONLY_LONG) long_tail(step_kind<ONLY_LONG>{});
+                else if (seq == LONG_START) long_tail(step_kind<LONG_START>{});
+                else long_tail(step_kind<LONG_STOP>{});
             } else {
                 imdct_short_wave(lane, ldsf, tb.aac_tw_short, lt);  // H[w] = ldsf[short_row(w) ..]
                 const float *sw = tabs + (shape ? kTabKbdShort : kTabSineShort);
@@ -407,26 +456,35 @@ __global__ __launch_bounds__(256, SYM_AAC_MIN_WAVES) void aac_synth_quad_kernel(
                 }
             }
         }
+        if constexpr (KIND == kStepHalo) {
+            wave_sync();  // (wave 3's own area: the next transform overwrites what this one read)
+        } else {
         wg_sync_lds();  // every delay line of this step is in its slot (LDS-only: the prefetch and the PCM stores stay in flight)
 
         // ---------------- phase 2: overlap-add with the predecessor's delay line, PCM out
-        if (active && emit) {
+        if (active) {
             float *frame_out = pcm + (chain_base + (size_t)t) * 1024;
+            float dst[2][8];
             if (seq != EIGHT_SHORT) {
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
                     const int m2 = lane + 64 * h;
-                    float dl[8], dst[8];
+                    float dl[8];
                     load_slot(prev_slot, m2, dl);
 #pragma unroll
-                    for (int q = 0; q < 8; ++q) {  // dsp.rs:105-129: dst = delay + pcm * w, or delay alone
-                        const int j = q < 4 ? 4 * m2 + q : 1020 - 4 * m2 + (q - 4);
-                        const float v = dl[q] + xw[h][q];
-                        dst[q] = (seq == LONG_STOP && j < kP0) ? dl[q] : v;
+                    for (int q = 0; q < 8; ++q) dst[h][q] = dl[q] + xw[h][q];  // dsp.rs:105-129: dst = delay + pcm * w ...
+                    if (seq == LONG_STOP) {                                     // ... or the delay alone (a uniform branch)
+#pragma unroll
+                        for (int q = 0; q < 8; ++q) {
+                            const int j = q < 4 ? 4 * m2 + q : 1020 - 4 * m2 + (q - 4);
+                            dst[h][q] = j < kP0 ? dl[q] : dst[h][q];
+                        }
                     }
-                    st_slot(frame_out, m2, dst);
                 }
             } else {
+                // The arithmetic stays rolled (unrolled it costs ~50 registers); the frame's PCM replaces the predecessor's delay line
+                // in its slot -- this wavefront is the slot's only reader, and the owner rewrites it behind the second barrier -- and
+                // is picked up in the long arms' slot order, so that both arms END in the same four stores below.
                 const float *sw = tabs + (shape ? kTabKbdShort : kTabSineShort);
                 const float *psw = tabs + (prev_shape ? kTabKbdShort : kTabSineShort);
 #pragma unroll 1
@@ -440,9 +498,17 @@ __global__ __launch_bounds__(256, SYM_AAC_MIN_WAVES) void aac_synth_quad_kernel(
 #pragma unroll
                         for (int q = 0; q < 4; ++q) o[q] = o[q] + ps[q];
                     }
-                    st_stream(reinterpret_cast<float4 *>(frame_out + j0), make_float4(o[0], o[1], o[2], o[3]));
+                    *reinterpret_cast<float4 *>(prev_slot + j0) = make_float4(o[0], o[1], o[2], o[3]);
                 }
+                wave_sync();
+#pragma unroll
+                for (int h = 0; h < 2; ++h) load_slot(prev_slot, lane + 64 * h, dst[h]);
             }
+            // Exactly four PCM stores per frame, on every path; the next frame's lines are claimed right behind them, in straight-line
+            // code: a wait for the lines alone, vmcnt(4).  (The side byte was requested in front of the lines: it has arrived when they have.)
+#pragma unroll
+            for (int h = 0; h < 2; ++h) st_slot(frame_out, lane + 64 * h, dst[h]);
+            if constexpr (KIND == kStepFull && !JS) settle_prefetch(line);
             if (t + 1 == (long)frames_per_chain) {  // the chain's last frame: its delay line is the outgoing state
                 float4 *d = reinterpret_cast<float4 *>(delay_out + (size_t)(ch ? chain1 : chain) * 1024);
 #pragma unroll
@@ -450,9 +516,17 @@ __global__ __launch_bounds__(256, SYM_AAC_MIN_WAVES) void aac_synth_quad_kernel(
             }
         }
         wg_sync_lds();  // the slots are free: the next transforms overwrite them
+        }
         }  // ch
-        if (active) t_loaded = tn < t_end ? tn : -100;
-    }
+    };
+
+    if (has_halo && wave == 3) step(step_kind<kStepHalo>{}, -1, t_begin - 1, true);
+    if constexpr (!JS) settle_prefetch(line);  // nothing is pending at the loop header, from either side
+    const int n_full = (int)((t_end - t_begin) >> 2);
+    long t = t_begin + wave;  // this wavefront's frame of step i
+#pragma unroll 1
+    for (int i = 0; i < n_full; ++i, t += 4) step(step_kind<kStepFull>{}, i, t, true);
+    if ((t_end - t_begin) & 3) step(step_kind<kStepRagged>{}, n_full, t, t < t_end);
 }
 
 // The per-chain index of a batch with channel pairs: .x = the partner chain, or -1 (after the memset) for a chain outside every
