@@ -33,6 +33,7 @@ mod flac;
 pub mod frontends;
 mod lookahead;
 mod mpa;
+mod pcm;
 mod vorbis;
 
 pub use aac::{AacFrontEnd, HipAacDecoder, ParsedAac};
@@ -42,6 +43,7 @@ pub use ctx::{Context, Pinned, Pool};
 pub use flac::{FlacFrontEnd, HipFlacDecoder, ParsedFlac};
 pub use lookahead::{find_reader, BatchCodec, Lookahead, LookaheadReader, PacketKey, Shared, SharedHandle, TrackQueue};
 pub use mpa::{HipMpaDecoder, MpaFrontEnd, ParsedMpa};
+pub use pcm::{SampleFormat, SourceSample};
 pub use vorbis::{HipVorbisDecoder, ParsedVorbis, VorbisFrontEnd};
 
 use symphonia_core::codecs::audio::AudioCodecId;

@@ -52,7 +52,7 @@
 extern "C" {
 #endif
 
-#define SYMACCEL_ABI_VERSION 8 /* 2: *_pp_device entry points, per-block status arrays, lookahead staging; 3: multi-GPU, probe; 4: mp3_decode_*device, vorbis floor_y; 5: aac_decode_pipelined, aac_joint_stereo_list, vorbis_decode; 6: batcher; 7: batch kinds for Vorbis from posts, FLAC and ALAC (symaccel_batch_slot has six input planes), lanes, per-ticket status; 8: *_strided_device (padded row pitch for the FLAC / ALAC planes), symaccel_row_stride; additions within 8: symaccel_md5_*, symaccel_flac_md5(_device) (STREAMINFO MD5) */
+#define SYMACCEL_ABI_VERSION 8 /* 2: *_pp_device entry points, per-block status arrays, lookahead staging; 3: multi-GPU, probe; 4: mp3_decode_*device, vorbis floor_y; 5: aac_decode_pipelined, aac_joint_stereo_list, vorbis_decode; 6: batcher; 7: batch kinds for Vorbis from posts, FLAC and ALAC (symaccel_batch_slot has six input planes), lanes, per-ticket status; 8: *_strided_device (padded row pitch for the FLAC / ALAC planes), symaccel_row_stride; additions within 8: symaccel_md5_*, symaccel_flac_md5(_device) (STREAMINFO MD5), SYMACCEL_FMT_*, symaccel_sample_bytes, symaccel_pcm_convert(_device), symaccel_batcher_reserve_fmt / _submit_fmt */
 
 typedef enum symaccel_status {
     SYMACCEL_OK = 0,
@@ -690,6 +690,45 @@ int symaccel_alac_mid_side_device(symaccel_ctx *ctx, const int32_t *d_weight, co
 int symaccel_alac_mid_side(symaccel_ctx *ctx, const int32_t *h_weight, const uint8_t *h_shift, int32_t *h_ch0,
                            int32_t *h_ch1, size_t n_pairs, size_t blocksize);
 
+/* ------------------------------------------------------------------ PCM in the caller's sample format
+ * Every decode path above ends in planar f32 PCM, or in left-justified i32 for FLAC and ALAC.  A consumer that plays or writes the
+ * audio wants interleaved samples of its device's format: the reference's copy_to_vec_interleaved / copy_bytes_to_vec_interleaved_as::<S>
+ * (symphonia-core/src/audio/generic.rs:204-340, the loops of audio/util.rs:119-167 and 245-331).  These entry points do that
+ * conversion and interleave on the device, so that what crosses the link is the bytes the consumer wants.
+ *
+ * Formats: a sample is symaccel_sample_bytes(fmt) bytes; the 24-bit formats are three packed little-endian bytes (sample.rs,
+ * to_ne_sample_bytes of i24 / u24 on a little-endian host).  Sources are SYMACCEL_FMT_F32 and SYMACCEL_FMT_S32 (the FLAC / ALAC planes
+ * as the library leaves them, already `<< (32 - bps)`); all nine are destinations.  Each of the 18 pairs is the reference's FromSample
+ * (audio/conv.rs:596-607 with clamp_f32 of util.rs:258-266 from f32 -- a NaN passes the clamp and becomes 0 in the cast, a float to
+ * integer cast truncates toward zero and saturates -- and conv.rs:521-532 from i32), bit for bit.  No dither (the reference's copy
+ * functions apply none). */
+#define SYMACCEL_FMT_U8 1
+#define SYMACCEL_FMT_S8 2
+#define SYMACCEL_FMT_U16 3
+#define SYMACCEL_FMT_S16 4
+#define SYMACCEL_FMT_U24 5
+#define SYMACCEL_FMT_S24 6
+#define SYMACCEL_FMT_U32 7
+#define SYMACCEL_FMT_S32 8
+#define SYMACCEL_FMT_F32 9
+/* 1, 1, 2, 2, 3, 3, 4, 4, 4 for the formats above in that order; 0 for anything else.  Pure arithmetic, no context. */
+size_t symaccel_sample_bytes(int fmt);
+/* n_groups interleave groups of `channels` (1..8) planes and n_frames frames: channel c of group g is the plane at d_src + (g * channels
+ * + c) * plane_stride SAMPLES (4 bytes each; plane_stride >= n_frames: the chain-major layout every entry point produces, or rows at
+ * symaccel_row_stride()); group g's output, [n_frames][channels] samples of dst_fmt, begins at d_dst + g * dst_group_bytes (>= n_frames *
+ * channels * symaccel_sample_bytes(dst_fmt)).  channels == 1 is a planar conversion; F32 -> F32 and S32 -> S32 copy (and interleave).
+ * d_src is 4-byte aligned; d_dst and dst_group_bytes are multiples of the sample size for the 2- and 4-byte formats and anything for
+ * the others (planes, strides and outputs that are multiples of 16 bytes take the fastest path).  Source and destination must not
+ * overlap, except for the in-place planar conversion between 4-byte formats (channels == 1, d_dst == d_src, dst_group_bytes ==
+ * plane_stride * 4).  Limits (they keep every extent in 64 bits): n_frames and plane_stride at most 2^36, n_groups at most 2^20,
+ * dst_group_bytes at most 2^40.  SYMACCEL_ERR_INVALID_ARG for anything else, unknown formats and sources other than F32 / S32 included. */
+int symaccel_pcm_convert_device(symaccel_ctx *ctx, const void *d_src, int src_fmt, size_t plane_stride, size_t n_groups,
+                                size_t channels, size_t n_frames, void *d_dst, int dst_fmt, size_t dst_group_bytes);
+/* The same between host buffers, staged through page-locked memory in chunks of whole groups (or of frames, for groups larger than a
+ * chunk), copy-in, kernel and copy-out overlapped. */
+int symaccel_pcm_convert(symaccel_ctx *ctx, const void *h_src, int src_fmt, size_t plane_stride, size_t n_groups, size_t channels,
+                         size_t n_frames, void *h_dst, int dst_fmt, size_t dst_group_bytes);
+
 /* ------------------------------------------------------------------ cross-stream batcher (csrc/batcher.cpp)
  * AudioDecoder::decode_ref (symphonia-core/src/codecs/audio.rs:279-297) sees one packet of one track and the registry builds
  * every decoder from (params, opts) alone (codecs/registry.rs:330-341): a decoder cannot see its siblings, so N decoders
@@ -815,6 +854,24 @@ int symaccel_batcher_wait(symaccel_batcher *b, uint64_t ticket, symaccel_batch_s
 int symaccel_batcher_release(symaccel_batcher *b, uint64_t ticket);
 int symaccel_batcher_submit(symaccel_batcher *b, int kind, int param, size_t n_chains, size_t units_per_chain,
                             const void **input, void **state_io, void *out, uint64_t *ticket); /* input[6], state_io[3] */
+/* reserve() / submit() with the PCM delivered in the caller's sample format (symaccel_pcm_convert_device, in the scatter of the launch: what
+ * crosses the link is the converted bytes).  out_fmt 0 = reserve() / submit(): the native planes.  Otherwise a SYMACCEL_FMT_*, channels
+ * 1..8 and n_chains % channels == 0: chains k * channels .. (k + 1) * channels - 1 of the submission form one interleave group, and the
+ * ticket's output is [n_chains / channels][samples_per_chain][channels] samples of out_fmt, the groups back to back at the front of
+ * slot.out (the region reserved for the native planes always holds it).  The six PCM kinds convert from F32, FLAC_RESTORE and
+ * ALAC_PREDICT from S32 (a group is one frame's subframes, samples_per_chain the padded block: units_per_chain); for the two Vorbis kinds
+ * samples_per_chain is what the chains' flags account for -- only that prefix is written -- and a submission whose chains of one
+ * interleave group disagree in it fails alone with SYMACCEL_ERR_INVALID_ARG: it runs as an empty description (its spectra / residue zeroed,
+ * for VORBIS_DECODE no floors and no coupling steps: silence), gets no PCM, and the state planes it returns are those of that silent run, of
+ * no use to the stream.  As in the native planes, the slots in front of a first block after a reset (lib.rs:298-303: n / 2 samples that no
+ * block writes) are counted in samples_per_chain and hold nothing defined -- here the conversion of device memory nobody wrote.  slot.out_bytes is the number of valid bytes: after wait()
+ * what was written (0 for a submission that failed), at reserve() the most the shape can give (for Vorbis the count is not known before
+ * the flags are written).  collect() copies exactly slot.out_bytes bytes to `out`.  State planes are never converted.  Submissions of
+ * any formats and groupings share the groups and launches of their (kind, param, units_per_chain). */
+int symaccel_batcher_reserve_fmt(symaccel_batcher *b, int kind, int param, size_t n_chains, size_t units_per_chain, int out_fmt,
+                                 int channels, symaccel_batch_slot *slot, uint64_t *ticket);
+int symaccel_batcher_submit_fmt(symaccel_batcher *b, int kind, int param, size_t n_chains, size_t units_per_chain, const void **input,
+                                void **state_io, void *out, int out_fmt, int channels, uint64_t *ticket); /* input[6], state_io[3] */
 /* submit() with the argument lists of the entry points the kinds stand for (symaccel_aac_synth, symaccel_mp3_synth,
  * symaccel_mp3_decode_pipelined for one stream: n_chains 1, or 2 = one channel pair with st_desc[granule]; st_desc may be NULL for 1) */
 int symaccel_batcher_submit_aac_synth(symaccel_batcher *b, const float *coeffs, const uint8_t *side, float *delay_io, float *pcm,

@@ -63,6 +63,22 @@ inline void check(int status, const symaccel_ctx *ctx = nullptr) {
     throw Error(status == SYMACCEL_ERR_UNSUPPORTED ? Error::Kind::Unsupported : Error::Kind::IoError, status, msg);
 }
 
+// The sample formats PCM can be delivered in (SYMACCEL_FMT_*; symphonia-core/src/audio/sample.rs: u8 .. f32, the 24-bit ones as three packed
+// little-endian bytes).  Native = the planes as the decoders leave them: planar f32, or left-justified i32 for FLAC.
+enum class SampleFormat : int {
+    Native = 0,
+    U8 = SYMACCEL_FMT_U8,
+    S8 = SYMACCEL_FMT_S8,
+    U16 = SYMACCEL_FMT_U16,
+    S16 = SYMACCEL_FMT_S16,
+    U24 = SYMACCEL_FMT_U24,
+    S24 = SYMACCEL_FMT_S24,
+    U32 = SYMACCEL_FMT_U32,
+    S32 = SYMACCEL_FMT_S32,
+    F32 = SYMACCEL_FMT_F32
+};
+inline std::size_t sample_bytes(SampleFormat f) { return symaccel_sample_bytes(static_cast<int>(f)); }
+
 // One context = one HIP device + stream + device-resident constant tables.  Externally synchronised, like
 // `&mut self` on the reference's decoders; distinct contexts may be used from distinct threads.
 class Context {
@@ -77,6 +93,13 @@ public:
     symaccel_ctx *raw() const { return ctx_; }
     void sync() { check(symaccel_sync(ctx_), ctx_); }
     void set_segment(int frames) { check(symaccel_ctx_set_segment(ctx_, frames), ctx_); }
+    // GenericAudioBufferRef::copy_bytes_to_vec_interleaved_as::<S> (audio/generic.rs:204-340) for planes in host memory: n_groups groups of
+    // `channels` planes (F32 or S32, plane_stride samples apart, n_frames valid) to [n_frames][channels] samples of `dst` per group,
+    // dst_group_bytes apart -- FromSample (audio/conv.rs) and the interleave (audio/util.rs:119-167) on the device
+    void pcm_convert(const void *h_src, SampleFormat src, std::size_t plane_stride, std::size_t n_groups, std::size_t channels, std::size_t n_frames, void *h_dst,
+                     SampleFormat dst, std::size_t dst_group_bytes) {
+        check(symaccel_pcm_convert(ctx_, h_src, static_cast<int>(src), plane_stride, n_groups, channels, n_frames, h_dst, static_cast<int>(dst), dst_group_bytes), ctx_);
+    }
 
 private:
     symaccel_ctx *ctx_ = nullptr;
@@ -520,6 +543,17 @@ struct AudioBufferRefT {  // GenericAudioBufferRef::F32 / ::S32 (audio/generic.r
 using AudioBufferRef = AudioBufferRefT<float>;          // the transform codecs
 using AudioBufferRefS32 = AudioBufferRefT<std::int32_t>;  // FLAC (AudioBuffer<i32>, flac/decoder.rs:103)
 
+// What last_decoded_bytes() of a decoder with an output format returns: the last packet as the bytes
+// copy_bytes_to_vec_interleaved_as::<S> would give for the buffer decode() returns (audio/generic.rs:204-340), in the batcher's
+// page-locked slot (valid, like every buffer of the trait, until the next &mut call).  Interleaved: `bytes` = frames * channels * sample
+// bytes at `data`.  Planar (set_output(f, false)): channel c's frames * sample bytes at data + c * plane_stride.
+struct DecodedBytes {
+    const std::uint8_t *data = nullptr;
+    std::size_t bytes = 0, frames = 0, channels = 0;
+    SampleFormat format = SampleFormat::Native;
+    std::size_t plane_stride = 0;  // bytes between the channels of a planar result; 0 = interleaved
+};
+
 struct FinalizeResult {  // codecs/audio.rs:230-236
     std::optional<bool> verify_ok;
 };
@@ -625,6 +659,23 @@ public:
 
     FinalizeResult finalize() { return FinalizeResult{}; }  // (the f32 codecs verify nothing, like the reference's)
     const Buffer &last_decoded() const { return last_; }
+    // Deliver the PCM in the caller's sample format, converted (and interleaved) in the batcher's scatter: what crosses the link is the
+    // bytes the caller wants (symaccel_batcher_reserve_fmt).  decode() then keeps returning the frame count, the planar ref holds no
+    // planes, and last_decoded_bytes() is the packet.  For decoders on a Batcher; between batches only: before the first decode() or
+    // right after reset().  SampleFormat::Native restores the planes.  (A FLAC stream that is not two channels wide is left-justified
+    // on the host, after the scatter: Error{Unsupported}.)
+    void set_output(SampleFormat format, bool interleaved = true) {
+        if (format != SampleFormat::Native) {
+            if (!batcher_ || Codec::kBatchKind == 0) throw std::invalid_argument("LookaheadDecoder::set_output: the conversion happens in the batcher's scatter");
+            if (sample_bytes(format) == 0 || codec_.channels() > 8) throw std::invalid_argument("LookaheadDecoder::set_output: format / channels");
+            if (!codec_.device_output_is_final()) throw Error(Error::Kind::Unsupported, SYMACCEL_ERR_UNSUPPORTED, "set_output: this stream's planes are finished on the host");
+        }
+        if (cur_live_ || next_live_ || head_ < ready_.size()) throw std::logic_error("LookaheadDecoder::set_output: between batches only (before decode() or after reset())");
+        out_fmt_ = format;
+        out_interleaved_ = interleaved;
+        clear_last();
+    }
+    const DecodedBytes &last_decoded_bytes() const { return bytes_; }
     std::size_t lookahead() const { return lookahead_; }
     std::size_t batches_run() const { return batches_; }
 
@@ -668,9 +719,7 @@ private:
     void submit(const std::vector<Packet> &batch) {
         if constexpr (Codec::kBatchKind != 0) {
             symaccel_batch_slot slot;
-            check(symaccel_batcher_reserve(batcher_->raw(), Codec::kBatchKind, codec_.batch_param(), codec_.batch_chains(batch.size()),
-                                           codec_.batch_units(batch.size()), &slot, &next_ticket_),
-                  ctx_.raw());
+            reserve(batch.size(), &slot, &next_ticket_);
             next_live_ = true;
             try {
                 codec_.fill_slot(batch, slot);  // the parsed packets and the carried state go into the page-locked slot
@@ -683,6 +732,17 @@ private:
             next_ids_.clear();
             for (const Packet &p : batch) next_ids_.push_back(Codec::id(p));
             hinted_ = false;
+        }
+    }
+    // a slot for a batch of n packets: the native planes, or (set_output) the interleave groups of the caller's format
+    void reserve(std::size_t n, symaccel_batch_slot *sl, std::uint64_t *t) {
+        if constexpr (Codec::kBatchKind != 0) {
+            if (out_fmt_ == SampleFormat::Native)
+                check(symaccel_batcher_reserve(batcher_->raw(), Codec::kBatchKind, codec_.batch_param(), codec_.batch_chains(n), codec_.batch_units(n), sl, t), ctx_.raw());
+            else
+                check(symaccel_batcher_reserve_fmt(batcher_->raw(), Codec::kBatchKind, codec_.batch_param(), codec_.batch_chains(n), codec_.batch_units(n),
+                                                   static_cast<int>(out_fmt_), out_interleaved_ ? (int)codec_.channels() : 1, sl, t),
+                      ctx_.raw());
         }
     }
     void replay_last() {
@@ -721,10 +781,6 @@ private:
             std::size_t k = head + std::min(lookahead_ - head, direct_.avail());
             if (k == 0) return;
             symaccel_batch_slot slot;
-            auto reserve = [&](std::size_t n, symaccel_batch_slot *sl, std::uint64_t *t) {
-                check(symaccel_batcher_reserve(batcher_->raw(), Codec::kBatchKind, codec_.batch_param(), codec_.batch_chains(n), codec_.batch_units(n), sl, t),
-                      ctx_.raw());
-            };
             reserve(k, &slot, &next_ticket_);
             next_live_ = true;
             next_ids_.clear();
@@ -782,7 +838,9 @@ private:
             cur_live_ = true;
             next_live_ = false;
             codec_.take_state(slot);
-            pcm_base_ = static_cast<const Sample *>(slot.out);
+            pcm_base_ = out_fmt_ == SampleFormat::Native ? static_cast<const Sample *>(slot.out) : nullptr;
+            out_base_ = static_cast<const std::uint8_t *>(slot.out);
+            out_valid_ = slot.out_bytes;
             ready_.swap(next_ids_);
             next_ids_.clear();
             batch_len_ = ready_.size();
@@ -814,13 +872,41 @@ private:
         // where packet i of the last batch lies in a channel's plane is the codec's business: fixed-size frames are
         // [channel][packet][frames]; Vorbis packs (prev_n + n) / 4 samples per packet and none for the first one
         const std::size_t nch = codec_.channels();
+        last_.frames = codec_.packet_frames(i);
+        if (out_fmt_ != SampleFormat::Native) {
+            if constexpr (Codec::kBatchKind != 0) {
+                // The converted slot holds the interleave groups back to back, each `per_chain` samples of every chain of it (the native
+                // plane's length; for Vorbis what the flags account for).  A packet is the frame range plane_offset() names in the
+                // native layout: chain = offset / native plane length, frames into the chain = the remainder.
+                last_.planes.assign(nch, nullptr);
+                const std::size_t sb = sample_bytes(out_fmt_), n_chains = codec_.batch_chains(batch_len_);
+                std::size_t native = 0;
+                check(symaccel_batcher_plane_bytes(Codec::kBatchKind, codec_.batch_param(), codec_.batch_units(batch_len_), nullptr, nullptr, &native), ctx_.raw());
+                native /= 4;
+                const std::size_t per_chain = out_valid_ / (n_chains * sb), at0 = codec_.plane_offset(0, i, batch_len_);
+                bytes_.frames = last_.frames;
+                bytes_.channels = nch;
+                bytes_.format = out_fmt_;
+                if (out_interleaved_) {
+                    bytes_.data = out_base_ + ((at0 / native / nch) * per_chain + at0 % native) * nch * sb;
+                    bytes_.bytes = last_.frames * nch * sb;
+                    bytes_.plane_stride = 0;
+                } else {
+                    const std::size_t at1 = nch > 1 ? codec_.plane_offset(1, i, batch_len_) : at0;
+                    bytes_.data = out_base_ + ((at0 / native) * per_chain + at0 % native) * sb;
+                    bytes_.bytes = last_.frames * sb;
+                    bytes_.plane_stride = ((at1 / native) - (at0 / native)) * per_chain * sb;
+                }
+            }
+            return;
+        }
         last_.planes.resize(nch);
         for (std::size_t c = 0; c < nch; ++c) last_.planes[c] = pcm_base_ + codec_.plane_offset(c, i, batch_len_);
-        last_.frames = codec_.packet_frames(i);
     }
     void clear_last() {
         last_.planes.assign(codec_.channels(), nullptr);
         last_.frames = 0;
+        bytes_ = DecodedBytes{};
     }
 
     Context &ctx_;
@@ -831,6 +917,11 @@ private:
     Direct direct_{};                        // (empty: the Peek form)
     std::vector<Sample> pcm_;                // [channel][packet of the batch][frames_per_packet]: planar per packet
     const Sample *pcm_base_ = nullptr;       // pcm_.data(), or the batcher's result slot of the current batch
+    SampleFormat out_fmt_ = SampleFormat::Native;  // set_output
+    bool out_interleaved_ = true;
+    const std::uint8_t *out_base_ = nullptr;  // the result slot as bytes, out_valid_ of them valid
+    std::size_t out_valid_ = 0;
+    DecodedBytes bytes_;
     std::vector<std::uint64_t> ready_;       // ids of the batch's packets, in order
     std::vector<std::uint64_t> next_ids_;    // ... of the batch submitted ahead
     std::uint64_t cur_ticket_ = 0, next_ticket_ = 0;
@@ -857,6 +948,7 @@ struct AacLc {
     explicit AacLc(const Params &p) : nch_(p.channels), delay_(p.channels * 1024, 0.0f) {}
     static std::uint64_t id(const Packet &p) { return p.ts; }
     std::size_t channels() const { return nch_; }
+    bool device_output_is_final() const { return true; }  // (set_output: slot.out is the PCM the trait hands out)
     std::size_t frames_per_packet() const { return 1024; }
     std::size_t packet_frames(std::size_t) const { return 1024; }
     std::size_t plane_offset(std::size_t c, std::size_t i, std::size_t k) const { return (c * k + i) * 1024; }
@@ -951,6 +1043,7 @@ struct AacLcCoded {
     }
     static std::uint64_t id(const Packet &p) { return p.ts; }
     std::size_t channels() const { return nch_; }
+    bool device_output_is_final() const { return true; }  // (set_output: slot.out is the PCM the trait hands out)
     std::size_t packet_frames(std::size_t) const { return 1024; }
     std::size_t plane_offset(std::size_t c, std::size_t i, std::size_t k) const { return (c * k + i) * 1024; }
     void reset_state() { std::fill(delay_.begin(), delay_.end(), 0.0f); }
@@ -1064,6 +1157,7 @@ struct Mp3 {
           vfront_(p.channels, 0) {}
     static std::uint64_t id(const Packet &p) { return p.ts; }
     std::size_t channels() const { return nch_; }
+    bool device_output_is_final() const { return true; }  // (set_output: slot.out is the PCM the trait hands out)
     std::size_t frames_per_packet() const { return 576 * ngr_; }
     std::size_t packet_frames(std::size_t) const { return 576 * ngr_; }
     std::size_t plane_offset(std::size_t c, std::size_t i, std::size_t k) const { return (c * k + i) * 576 * ngr_; }
@@ -1176,6 +1270,7 @@ struct Mp3Huffman {
     }
     static std::uint64_t id(const Packet &p) { return p.ts; }
     std::size_t channels() const { return nch_; }
+    bool device_output_is_final() const { return true; }  // (set_output: slot.out is the PCM the trait hands out)
     std::size_t packet_frames(std::size_t) const { return 576 * ngr_; }
     std::size_t plane_offset(std::size_t c, std::size_t i, std::size_t k) const { return (c * k + i) * 576 * ngr_; }
     void reset_state() {
@@ -1311,6 +1406,7 @@ struct Vorbis {
         : nch_(p.channels), e0_(p.bs0_exp), e1_(p.bs1_exp), prev_(p.channels, -1), overlap_(p.channels * ((std::size_t)1 << (p.bs1_exp - 1)), 0.0f) {}
     static std::uint64_t id(const Packet &p) { return p.ts; }
     std::size_t channels() const { return nch_; }
+    bool device_output_is_final() const { return true; }  // (set_output: slot.out is the PCM the trait hands out)
     std::size_t packet_frames(std::size_t i) const { return emits_[i] ? off_[i + 1] - off_[i] : 0; }
     std::size_t plane_offset(std::size_t c, std::size_t i, std::size_t) const { return c * stride_ + off_[i]; }
     void reset_state() {  // Dsp::reset (dsp.rs:45-56): no block to lap with, overlap zeroed
@@ -1482,6 +1578,7 @@ struct Flac {
     }
     static std::uint64_t id(const Packet &p) { return p.ts; }
     std::size_t channels() const { return nch_; }
+    bool device_output_is_final() const { return nch_ == 2; }  // (set_output: other layouts are left-justified on the host, take_state)
     std::size_t packet_frames(std::size_t i) const { return lens_[i]; }
     std::size_t plane_offset(std::size_t c, std::size_t i, std::size_t) const { return (i * nch_ + c) * stride_; }
     void reset_state() {}

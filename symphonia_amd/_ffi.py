@@ -25,6 +25,9 @@ TABLE_AAC_KBD_LONG, TABLE_AAC_KBD_SHORT, TABLE_AAC_SINE_LONG, TABLE_AAC_SINE_SHO
 TABLE_MP3_SYNTH_D, TABLE_MP3_IMDCT_WIN, TABLE_VORBIS_FLOOR1_DB, TABLE_MP3_CONSTS = 4, 5, 6, 7
 TABLE_MP3_POW43, TABLE_MP3_POW2AB = 8, 9
 
+# SYMACCEL_FMT_*: the sample formats PCM can be delivered in (symaccel_pcm_convert)
+FMT_U8, FMT_S8, FMT_U16, FMT_S16, FMT_U24, FMT_S24, FMT_U32, FMT_S32, FMT_F32 = range(1, 10)
+
 # every symbol include/symaccel.h declares (tests/test_abi.py checks the built library exports all)
 ABI_SYMBOLS = [
     "symaccel_abi_version", "symaccel_strerror", "symaccel_last_error", "symaccel_ctx_create",
@@ -56,6 +59,8 @@ ABI_SYMBOLS = [
     "symaccel_batcher_submit_vorbis_decode", "symaccel_batcher_submit_flac_restore", "symaccel_batcher_submit_alac_predict",
     "symaccel_flac_restore_strided_device", "symaccel_alac_predict_strided_device", "symaccel_row_stride",
     "symaccel_md5_init", "symaccel_md5_update", "symaccel_md5_digest", "symaccel_flac_md5_device", "symaccel_flac_md5",
+    "symaccel_sample_bytes", "symaccel_pcm_convert_device", "symaccel_pcm_convert",
+    "symaccel_batcher_reserve_fmt", "symaccel_batcher_submit_fmt",
 ]
 
 _vp, _sz, _i, _d, _u32 = C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.c_uint32
@@ -140,6 +145,8 @@ class Library:
         d.symaccel_batcher_wait.argtypes = [_vp, C.c_uint64, _vp]
         d.symaccel_batcher_release.argtypes = [_vp, C.c_uint64]
         d.symaccel_batcher_submit.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _vp, _vp, C.POINTER(C.c_uint64)]
+        d.symaccel_batcher_reserve_fmt.argtypes = [_vp, _i, _i, _sz, _sz, _i, _i, _vp, C.POINTER(C.c_uint64)]
+        d.symaccel_batcher_submit_fmt.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _vp, _vp, _i, _i, C.POINTER(C.c_uint64)]
         d.symaccel_batcher_collect.argtypes = [_vp, C.c_uint64]
         d.symaccel_batcher_abandon.argtypes = [_vp, C.c_uint64]
         d.symaccel_batcher_submit_aac_synth.argtypes = [_vp, _vp, _vp, _vp, _vp, _sz, _sz, C.POINTER(C.c_uint64)]
@@ -225,6 +232,10 @@ class Library:
         d.symaccel_md5_digest.argtypes = [_vp, _vp]
         d.symaccel_flac_md5_device.argtypes = [_vp, _vp, _sz]
         d.symaccel_flac_md5.argtypes = [_vp, _vp, _sz, _vp, _sz, _i, _i, _vp, _vp]
+        d.symaccel_sample_bytes.argtypes = [_i]
+        d.symaccel_sample_bytes.restype = _sz
+        d.symaccel_pcm_convert_device.argtypes = [_vp, _vp, _i, _sz, _sz, _sz, _sz, _vp, _i, _sz]
+        d.symaccel_pcm_convert.argtypes = [_vp, _vp, _i, _sz, _sz, _sz, _sz, _vp, _i, _sz]
         d.symaccel_alac_block_status_device.argtypes = [_vp, _vp, _sz, _vp]
         d.symaccel_vorbis_floor1_status_device.argtypes = [_vp, _i, _vp, _sz, _vp]
         d.symaccel_aac_tns_status_device.argtypes = [_vp, _sz, _vp, _sz, _vp]

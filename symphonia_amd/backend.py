@@ -703,6 +703,52 @@ def flac_md5_device(ctx, jobs, n_jobs=None):
     ctx._call(ctx.lib.dll.symaccel_flac_md5_device, _ptr(jobs), n)
 
 
+# ---- PCM in the caller's sample format (symaccel_pcm_convert) --------------------------------------------------------------------
+FMT_U8, FMT_S8, FMT_U16, FMT_S16, FMT_U24, FMT_S24, FMT_U32, FMT_S32, FMT_F32 = (_ffi.FMT_U8, _ffi.FMT_S8, _ffi.FMT_U16, _ffi.FMT_S16, _ffi.FMT_U24,
+                                                                                 _ffi.FMT_S24, _ffi.FMT_U32, _ffi.FMT_S32, _ffi.FMT_F32)
+SAMPLE_FORMATS = {"u8": FMT_U8, "s8": FMT_S8, "u16": FMT_U16, "s16": FMT_S16, "u24": FMT_U24, "s24": FMT_S24, "u32": FMT_U32, "s32": FMT_S32,
+                  "f32": FMT_F32}
+
+
+def sample_format(fmt):
+    """A SYMACCEL_FMT_* value from a value or a name ("s16", "f32", ...)."""
+    return SAMPLE_FORMATS[fmt.lower()] if isinstance(fmt, str) else int(fmt)
+
+
+def sample_bytes(fmt, lib=None):
+    """symaccel_sample_bytes: bytes per sample of a format (the 24-bit formats are three packed bytes); 0 for an unknown one."""
+    lib = lib if lib is not None else _ffi.default_library()
+    return int(lib.dll.symaccel_sample_bytes(sample_format(fmt)))
+
+
+def pcm_convert(ctx, planes, dst_fmt, channels=1, n_frames=None, src_fmt=None):
+    """symaccel_pcm_convert: planes[n_groups * channels, plane_stride] in host memory, float32 (FMT_F32) or int32 (FMT_S32, left-justified
+    as FLAC / ALAC leave it), to uint8[n_groups, n_frames * channels * sample_bytes]: every group's `channels` planes converted with the
+    reference's FromSample (audio/conv.rs) and interleaved frame by frame -- what copy_bytes_to_vec_interleaved_as::<S> returns
+    (audio/generic.rs:204-340).  n_frames defaults to the whole row."""
+    p = np.ascontiguousarray(planes)
+    if p.ndim != 2 or p.dtype not in (np.float32, np.int32):
+        raise ValueError("planes must be a [n_groups * channels, plane_stride] array of float32 or int32")
+    src_fmt = (FMT_F32 if p.dtype == np.float32 else FMT_S32) if src_fmt is None else sample_format(src_fmt)
+    dst_fmt, channels = sample_format(dst_fmt), int(channels)
+    nf = p.shape[1] if n_frames is None else int(n_frames)
+    if channels < 1 or p.shape[0] % channels or not 0 <= nf <= p.shape[1]:
+        raise ValueError("%d planes of %d samples do not hold groups of %d channels x %d frames" % (p.shape[0], p.shape[1], channels, nf))
+    group_bytes = nf * channels * sample_bytes(dst_fmt, ctx.lib)
+    out = np.zeros((p.shape[0] // channels, group_bytes), np.uint8)
+    ctx._call(ctx.lib.dll.symaccel_pcm_convert, _ptr(p), src_fmt, p.shape[1], out.shape[0], channels, nf, _ptr(out), dst_fmt, group_bytes)
+    return out
+
+
+def pcm_convert_device(ctx, src, src_fmt, plane_stride, n_groups, channels, n_frames, dst, dst_fmt, dst_group_bytes, dst_offset=0):
+    """symaccel_pcm_convert_device on device memory (torch tensors, or raw addresses): channel c of group g is the plane at src + (g *
+    channels + c) * plane_stride samples, group g's [n_frames][channels] samples of dst_fmt go to dst + dst_offset + g * dst_group_bytes.
+    Asynchronous on the context's stream."""
+    d = dst if isinstance(dst, int) else _ptr(dst)
+    ctx._call(ctx.lib.dll.symaccel_pcm_convert_device, src if isinstance(src, int) else _ptr(src), sample_format(src_fmt), int(plane_stride),
+              int(n_groups), int(channels), int(n_frames), (d + int(dst_offset)) if d is not None else None, sample_format(dst_fmt), int(dst_group_bytes))
+
+
 ALAC_DESC_DTYPE = np.dtype([("mode", np.uint8), ("lpc_order", np.uint8), ("shift", np.uint8), ("bps", np.uint8)])
 
 
@@ -912,16 +958,23 @@ class Batcher:
     def _check(self, st):
         return self.ctx.lib.check(st, self.ctx.handle)
 
-    def submit(self, kind, param, inputs, states, out):
+    def submit(self, kind, param, inputs, states, out, out_format=0, channels=0, n_chains=None, units=None):
         """inputs / states / out: C-contiguous numpy arrays ([chain][unit]... / [chain]...); the states are updated and `out` is
-        filled by collect()."""
-        n_chains, units = int(out.shape[0]), int(out.shape[1])
+        filled by collect().  out_format (a FMT_* value or name) / channels: symaccel_batcher_submit_fmt -- `out` then receives
+        [n_chains / channels][samples][channels] samples of that format (a byte buffer of the native planes' size always holds it) and
+        n_chains / units are taken from inputs[0]'s shape unless given."""
+        shaped = out if not out_format else inputs[0]
+        n_chains, units = int(shaped.shape[0] if n_chains is None else n_chains), int(shaped.shape[1] if units is None else units)
         ins = (C.c_void_p * 6)(*[a.ctypes.data if a is not None else None for a in list(inputs) + [None] * (6 - len(inputs))])
         sts = (C.c_void_p * 3)(*[a.ctypes.data for a in list(states)] + [None] * (3 - len(states)))
         for a in list(inputs) + list(states) + [out]:
             assert a is None or a.flags["C_CONTIGUOUS"]
         t = C.c_uint64()
-        self._check(self.dll.symaccel_batcher_submit(self.handle, int(kind), int(param), n_chains, units, ins, sts, out.ctypes.data, C.byref(t)))
+        if out_format:
+            self._check(self.dll.symaccel_batcher_submit_fmt(self.handle, int(kind), int(param), n_chains, units, ins, sts, out.ctypes.data,
+                                                             sample_format(out_format), int(channels), C.byref(t)))
+        else:
+            self._check(self.dll.symaccel_batcher_submit(self.handle, int(kind), int(param), n_chains, units, ins, sts, out.ctypes.data, C.byref(t)))
         return int(t.value)
 
     def collect(self, ticket):
@@ -1005,9 +1058,15 @@ class Batcher:
             pair_shift.ctypes.data if pair_shift is not None else None, n_blocks, blocksize, C.byref(t)))
         return int(t.value)
 
-    def reserve(self, kind, param, n_chains, units):
+    def reserve(self, kind, param, n_chains, units, out_format=0, channels=0):
+        """out_format / channels: symaccel_batcher_reserve_fmt -- slot.out then receives interleaved samples of that format, slot.out_bytes
+        of them valid (wait() returns the count the launch wrote)"""
         slot, t = BatchSlot(), C.c_uint64()
-        self._check(self.dll.symaccel_batcher_reserve(self.handle, int(kind), int(param), int(n_chains), int(units), C.byref(slot), C.byref(t)))
+        if out_format:
+            self._check(self.dll.symaccel_batcher_reserve_fmt(self.handle, int(kind), int(param), int(n_chains), int(units), sample_format(out_format),
+                                                              int(channels), C.byref(slot), C.byref(t)))
+        else:
+            self._check(self.dll.symaccel_batcher_reserve(self.handle, int(kind), int(param), int(n_chains), int(units), C.byref(slot), C.byref(t)))
         return int(t.value), slot
 
     def commit(self, ticket):

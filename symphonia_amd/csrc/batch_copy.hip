@@ -9,21 +9,16 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "pcm_convert.h"
 #include "symaccel_internal.h"
 
 namespace symaccel {
 
 namespace {
 
-// A capped grid walks the piece list: the link needs about a hundred KiB in flight (50 GB/s x 2 us), not the 32 MiB a grid of one
-// workgroup per piece keeps resident -- such a grid fills every wave slot of the device with workgroups that wait for PCIe, and the
-// scatter and the synthesis kernel of the neighbouring chunk (other streams) queue behind it instead of running beside it.
-// (DIR -- 0 = gather, host to device; 1 = scatter -- changes nothing in the code: it names the two directions apart in a kernel trace)
-template <bool NT, int DIR>
-__global__ __launch_bounds__(256) void batch_copy_kernel(const BatchCopyDesc *__restrict__ descs, unsigned n_pieces) {
-  for (unsigned piece = blockIdx.x; piece < n_pieces; piece += gridDim.x) {
-    const BatchCopyDesc d = descs[piece];
-    const unsigned tid = threadIdx.x;
+// one piece, by the 256 work-items of a workgroup
+template <bool NT>
+__device__ __forceinline__ void batch_copy_piece(const BatchCopyDesc d, const unsigned tid) {
     const uintptr_t s = reinterpret_cast<uintptr_t>(d.src), t = reinterpret_cast<uintptr_t>(d.dst);
     if (((s | t | d.bytes) & 15u) == 0) {
         const uint4 *src = reinterpret_cast<const uint4 *>(d.src);
@@ -62,8 +57,155 @@ __global__ __launch_bounds__(256) void batch_copy_kernel(const BatchCopyDesc *__
         uint8_t *dst = reinterpret_cast<uint8_t *>(d.dst);
         for (unsigned i = tid; i < d.bytes; i += 256u) dst[i] = src[i];
     }
+}
+
+// A capped grid walks the piece list: the link needs about a hundred KiB in flight (50 GB/s x 2 us), not the 32 MiB a grid of one
+// workgroup per piece keeps resident -- such a grid fills every wave slot of the device with workgroups that wait for PCIe, and the
+// scatter and the synthesis kernel of the neighbouring chunk (other streams) queue behind it instead of running beside it.
+// (DIR -- 0 = gather, host to device; 1 = scatter -- changes nothing in the code: it names the two directions apart in a kernel trace)
+template <bool NT, int DIR>
+__global__ __launch_bounds__(256) void batch_copy_kernel(const BatchCopyDesc *__restrict__ descs, unsigned n_pieces) {
+  for (unsigned piece = blockIdx.x; piece < n_pieces; piece += gridDim.x) {
+    const BatchCopyDesc d = descs[piece];
+    batch_copy_piece<NT>(d, threadIdx.x);
   }
 }
+
+// PCM in the caller's sample format (pcm_convert.h): a capped grid walks the tiles of every interleave group -- a tile is a frame range
+// of one group whose output is contiguous and at most kPcmTileBytes long.  One instantiation per (source, destination) pair: nothing
+// is decided per sample.
+struct PcmConvertArgs {
+    const uint32_t *src;
+    uint8_t *dst;
+    size_t plane_stride, n_frames, dst_group_bytes, n_groups, tiles_per_group;
+    unsigned channels, tile_frames;
+};
+
+template <int SRC, int DST>
+__global__ __launch_bounds__(256) void pcm_convert_kernel(const PcmConvertArgs a) {
+    __shared__ uint32_t image[kPcmLdsDwords];
+    // (blockIdx.y strides over the groups, blockIdx.x over a group's tiles: no division to find a tile's group)
+    for (size_t g = blockIdx.y; g < a.n_groups; g += gridDim.y)
+        for (size_t tile = blockIdx.x; tile < a.tiles_per_group; tile += gridDim.x) {
+            const size_t f0 = tile * a.tile_frames;
+            const unsigned nf = a.n_frames - f0 < a.tile_frames ? (unsigned)(a.n_frames - f0) : a.tile_frames;
+            pcm_tile<SRC, DST>(a.src + g * a.channels * a.plane_stride + f0, a.plane_stride, a.channels, nf,
+                               a.dst + g * a.dst_group_bytes + f0 * a.channels * pcm_sample_bytes(DST), image);
+        }
+}
+
+template <int SRC>
+void pcm_convert_launch(int dst_fmt, dim3 grid, hipStream_t stream, const PcmConvertArgs &a) {
+    switch (dst_fmt) {
+#define SYM_PCM_CASE(F) \
+    case F: hipLaunchKernelGGL((pcm_convert_kernel<SRC, F>), grid, dim3(256), 0, stream, a); break;
+        SYM_PCM_CASE(SYMACCEL_FMT_U8)
+        SYM_PCM_CASE(SYMACCEL_FMT_S8)
+        SYM_PCM_CASE(SYMACCEL_FMT_U16)
+        SYM_PCM_CASE(SYMACCEL_FMT_S16)
+        SYM_PCM_CASE(SYMACCEL_FMT_U24)
+        SYM_PCM_CASE(SYMACCEL_FMT_S24)
+        SYM_PCM_CASE(SYMACCEL_FMT_U32)
+        SYM_PCM_CASE(SYMACCEL_FMT_S32)
+        SYM_PCM_CASE(SYMACCEL_FMT_F32)
+#undef SYM_PCM_CASE
+    }
+}
+
+// The scatter of a chunk that holds converting pieces (BatchCopyDesc::pad != 0: batcher.cpp, tickets with an output format): `src` is
+// the first frame of the piece in the first plane of its interleave group -- the other planes follow `plane_stride` samples apart, the
+// same for every piece of a launch --, `dst` and `bytes` the piece's contiguous output in the page-locked slot.  Plain pieces are copied
+// as batch_copy_kernel copies them.  The choice is per piece, the same for the whole workgroup.
+// batch_copy_piece<false> for the kernel below, with its four 16-byte values in named registers: beside the tile routines the compiler
+// keeps the `uint4 v[4]` of batch_copy_piece in scratch memory (80 bytes a lane) and waits for every load before the next.  It is a second
+// copy of that routine on purpose: rewriting batch_copy_piece itself would change the kernel every chunk WITHOUT a converting piece runs
+// (batch_copy_kernel, unchanged to the instruction), for the sake of the chunks with one.  What follows from it: the plain pieces that
+// share a chunk with a converting ticket -- state planes, the PCM of tickets without a format -- are copied by this routine, same access
+// pattern, and the development knob SYMACCEL_BATCH_COPY_NT (non-temporal accesses) does not reach such chunks.
+__device__ __forceinline__ void batch_copy_piece_beside_tiles(const BatchCopyDesc d, const unsigned tid) {
+    const uintptr_t s = reinterpret_cast<uintptr_t>(d.src), t = reinterpret_cast<uintptr_t>(d.dst);
+    if (((s | t | d.bytes) & 15u) == 0) {
+        const uint4 *src = reinterpret_cast<const uint4 *>(d.src);
+        uint4 *dst = reinterpret_cast<uint4 *>(d.dst);
+        const unsigned n = d.bytes / 16u;  // <= 1024
+        const bool p0 = tid < n, p1 = tid + 256u < n, p2 = tid + 512u < n, p3 = tid + 768u < n;
+        uint4 v0 = {}, v1 = {}, v2 = {}, v3 = {};
+        if (p0) v0 = src[tid];
+        if (p1) v1 = src[tid + 256u];
+        if (p2) v2 = src[tid + 512u];
+        if (p3) v3 = src[tid + 768u];
+        if (p0) dst[tid] = v0;
+        if (p1) dst[tid + 256u] = v1;
+        if (p2) dst[tid + 512u] = v2;
+        if (p3) dst[tid + 768u] = v3;
+    } else if (((s | t | d.bytes) & 3u) == 0) {
+        const uint32_t *src = reinterpret_cast<const uint32_t *>(d.src);
+        uint32_t *dst = reinterpret_cast<uint32_t *>(d.dst);
+        for (unsigned i = tid; i < d.bytes / 4u; i += 256u) dst[i] = src[i];
+    } else {
+        const uint8_t *src = reinterpret_cast<const uint8_t *>(d.src);
+        uint8_t *dst = reinterpret_cast<uint8_t *>(d.dst);
+        for (unsigned i = tid; i < d.bytes; i += 256u) dst[i] = src[i];
+    }
+}
+
+template <int SRC>
+__device__ __forceinline__ void batch_convert_piece(const BatchCopyDesc d, size_t plane_stride, uint32_t *image) {
+    const unsigned channels = (d.pad >> 8) & 15u, dst_fmt = d.pad & 15u, frames = (d.pad >> 12) & 0x1fffu;
+    const uint32_t *src = static_cast<const uint32_t *>(d.src);
+    uint8_t *dst = static_cast<uint8_t *>(d.dst);
+    switch (dst_fmt) {
+#define SYM_PCM_CASE(F) \
+    case F: pcm_tile_lds<SRC, F>(src, plane_stride, channels, frames, dst, image); break;
+        SYM_PCM_CASE(SYMACCEL_FMT_U8)
+        SYM_PCM_CASE(SYMACCEL_FMT_S8)
+        SYM_PCM_CASE(SYMACCEL_FMT_U16)
+        SYM_PCM_CASE(SYMACCEL_FMT_S16)
+        SYM_PCM_CASE(SYMACCEL_FMT_U24)
+        SYM_PCM_CASE(SYMACCEL_FMT_S24)
+        SYM_PCM_CASE(SYMACCEL_FMT_U32)
+        SYM_PCM_CASE(SYMACCEL_FMT_S32)
+        SYM_PCM_CASE(SYMACCEL_FMT_F32)
+#undef SYM_PCM_CASE
+    }
+}
+
+__global__ __launch_bounds__(256) void batch_scatter_convert_kernel(const BatchCopyDesc *__restrict__ descs, unsigned n_pieces, size_t plane_stride) {
+    __shared__ uint32_t image[kPcmLdsDwords];
+    for (unsigned piece = blockIdx.x; piece < n_pieces; piece += gridDim.x) {
+        const BatchCopyDesc d = descs[piece];
+        if (d.pad == 0) batch_copy_piece_beside_tiles(d, threadIdx.x);
+        else if (d.pad & kBatchPieceFromI32) batch_convert_piece<SYMACCEL_FMT_S32>(d, plane_stride, image);
+        else batch_convert_piece<SYMACCEL_FMT_F32>(d, plane_stride, image);
+    }
+}
+
+}  // namespace
+
+// (the caller has checked formats, channel count, alignment and sizes: symaccel_pcm_convert_device)
+int launch_pcm_convert(symaccel_ctx *ctx, hipStream_t stream, const void *d_src, int src_fmt, size_t plane_stride, size_t n_groups, size_t channels,
+                       size_t n_frames, void *d_dst, int dst_fmt, size_t dst_group_bytes) {
+    if (n_groups == 0 || n_frames == 0) return SYMACCEL_OK;
+    PcmConvertArgs a;
+    a.src = static_cast<const uint32_t *>(d_src);
+    a.dst = static_cast<uint8_t *>(d_dst);
+    a.plane_stride = plane_stride;
+    a.n_frames = n_frames;
+    a.dst_group_bytes = dst_group_bytes;
+    a.channels = (unsigned)channels;
+    a.tile_frames = pcm_tile_frames((unsigned)channels, pcm_sample_bytes(dst_fmt));
+    a.n_groups = n_groups;
+    a.tiles_per_group = (n_frames + a.tile_frames - 1) / a.tile_frames;
+    // eight workgroups per compute unit keep every wave slot a 256-lane workgroup with a 16 KiB image can have busy; more only queue
+    const size_t cap = (size_t)ctx->n_cus * 8, gx = std::min(a.tiles_per_group, cap);
+    const dim3 grid((unsigned)gx, (unsigned)std::min<size_t>(n_groups, std::max<size_t>(1, cap / gx)));
+    if (src_fmt == SYMACCEL_FMT_F32) pcm_convert_launch<SYMACCEL_FMT_F32>(dst_fmt, grid, stream, a);
+    else pcm_convert_launch<SYMACCEL_FMT_S32>(dst_fmt, grid, stream, a);
+    SYM_GPU(ctx, hipGetLastError());
+    return SYMACCEL_OK;
+}
+
+namespace {
 
 // The completion flag of a launch: ONE 64-bit word in page-locked host memory, written behind the last scatter of the launch (same
 // stream: the scatter's stores to host memory are complete when this kernel starts).  Waiters read the word -- no runtime call on the
@@ -81,7 +223,7 @@ int launch_batch_flag(symaccel_ctx *ctx, hipStream_t stream, uint64_t *h_flag, u
     return SYMACCEL_OK;
 }
 
-int launch_batch_copy(symaccel_ctx *ctx, hipStream_t stream, const BatchCopyDesc *descs, size_t n, bool scatter) {
+int launch_batch_copy(symaccel_ctx *ctx, hipStream_t stream, const BatchCopyDesc *descs, size_t n, bool scatter, size_t pcm_plane_stride) {
     if (n == 0) return SYMACCEL_OK;
     if (n > 0x7fffffffu) return SYMACCEL_ERR_INVALID_ARG;
     // workgroups per copy launch.  64: the link needs few -- a copy kernel that fills the device keeps the synthesis kernel and the copy of
@@ -97,7 +239,9 @@ int launch_batch_copy(symaccel_ctx *ctx, hipStream_t stream, const BatchCopyDesc
         const char *e = std::getenv("SYMACCEL_BATCH_COPY_NT");
         return e && std::atoi(e) != 0;
     }();
-    if (nt && scatter) hipLaunchKernelGGL((batch_copy_kernel<true, 1>), dim3(grid), dim3(256), 0, stream, descs, (unsigned)n);
+    // (pcm_plane_stride != 0: the list holds converting pieces -- only then; every other launch is the plain kernel, as before)
+    if (pcm_plane_stride) hipLaunchKernelGGL(batch_scatter_convert_kernel, dim3(grid), dim3(256), 0, stream, descs, (unsigned)n, pcm_plane_stride);
+    else if (nt && scatter) hipLaunchKernelGGL((batch_copy_kernel<true, 1>), dim3(grid), dim3(256), 0, stream, descs, (unsigned)n);
     else if (nt) hipLaunchKernelGGL((batch_copy_kernel<true, 0>), dim3(grid), dim3(256), 0, stream, descs, (unsigned)n);
     else if (scatter) hipLaunchKernelGGL((batch_copy_kernel<false, 1>), dim3(grid), dim3(256), 0, stream, descs, (unsigned)n);
     else hipLaunchKernelGGL((batch_copy_kernel<false, 0>), dim3(grid), dim3(256), 0, stream, descs, (unsigned)n);

@@ -264,6 +264,11 @@ struct Ticket {
     // copy form (symaccel_batcher_submit): where collect() puts the results
     void *user_state[kMaxState] = {nullptr, nullptr, nullptr};
     void *user_out = nullptr;
+    // the output format asked for (symaccel_batcher_reserve_fmt; 0 = the native planes), the chains of an interleave group, and the bytes
+    // of slot.out that are valid: the most the shape can give at reserve(), what the launch wrote afterwards
+    int out_fmt = 0;
+    uint32_t channels = 0;
+    size_t out_valid = 0;
 };
 
 // what a launch needs of a submission: copied out of the ticket table when the group closes, because the launch runs outside the
@@ -272,6 +277,10 @@ struct TicketView {
     char *slot = nullptr;
     uint32_t first_chain = 0, n_chains = 0;
     int status = SYMACCEL_OK;
+    int out_fmt = 0;
+    uint32_t channels = 0;
+    size_t out_valid = 0;
+    int fmt_status = SYMACCEL_OK;  // what the output format has to say about the submission (Vorbis: an interleave group whose chains disagree)
 };
 
 enum class GroupState { Free, Open, Closed, Launching, Launched };
@@ -838,6 +847,33 @@ int launch_group_inner(Lane *lane, Group *g, uint64_t *n_chunks, uint64_t *api_n
         bound += 2 * g->chains;  // (each row rounded up)
     }
     if (g->kind == SYMACCEL_BATCH_VORBIS_SYNTH || g->kind == SYMACCEL_BATCH_VORBIS_DECODE) bound += 2 * g->chains;  // (spectra and PCM go chain by chain, each rounded up)
+    // Submissions with an output format (symaccel_batcher_reserve_fmt): their PCM leaves as converting pieces, a frame range of one
+    // interleave group each.  What a Vorbis chain's flags account for is read here, in front of the first chunk (the scatter of a chunk
+    // overwrites the state planes the count depends on); a submission whose chains of one interleave group disagree fails alone.
+    const bool vorbis_kind = g->kind == SYMACCEL_BATCH_VORBIS_SYNTH || g->kind == SYMACCEL_BATCH_VORBIS_DECODE;
+    const size_t native_samples = (ps.in_place ? ps.in[0] : ps.out) / 4;
+    for (TicketView &v : views) {
+        if (!v.out_fmt) continue;
+        const size_t fb = (size_t)v.channels * symaccel_sample_bytes(v.out_fmt);
+        bound += (v.n_chains / v.channels) * ((native_samples + pcm_tile_frames(v.channels, (unsigned)symaccel_sample_bytes(v.out_fmt)) - 1) /
+                                              pcm_tile_frames(v.channels, (unsigned)symaccel_sample_bytes(v.out_fmt)) + 1);
+        v.out_valid = (v.n_chains / v.channels) * native_samples * fb;
+        if (vorbis_kind) {
+            const SlotLayout l = slot_layout(ps, v.n_chains);
+            v.out_valid = 0;
+            size_t first = 0;  // what the first chain of the current interleave group accounts for
+            for (size_t c = 0; c < v.n_chains; ++c) {
+                size_t lines, samples;
+                vorbis_used(reinterpret_cast<const uint8_t *>(v.slot + l.in[1]) + c * g->units, g->units, reinterpret_cast<const int32_t *>(v.slot + l.state[0])[c],
+                            g->param & 255, (g->param >> 8) & 255, &lines, &samples);
+                if (c % v.channels == 0) first = samples, v.out_valid += samples * fb;
+                else if (samples != first) v.fmt_status = SYMACCEL_ERR_INVALID_ARG;
+            }
+            // like every other per-ticket failure it runs as an empty description: silence in (VORBIS_DECODE: no floors and no steps either,
+            // through its status below), nothing of the stream's data reaches the kernels, and no PCM comes back
+            if (v.fmt_status != SYMACCEL_OK) std::memset(v.slot + l.in[0], 0, l.in_bytes[0]);
+        }
+    }
     g->aac_pairs = g->aac_tns = 0;
     g->vb_steps = 0;
     // ---- the submissions' own descriptors, each judged alone: one that does not add up is neutralised (it runs as an empty
@@ -868,6 +904,8 @@ int launch_group_inner(Lane *lane, Group *g, uint64_t *n_chunks, uint64_t *api_n
         bound += 6 * (g->tickets + 8) + pieces_of(ls.vb_boff) + pieces_of(ls.vb_kill) + pieces_of(ls.vb_first) + pieces_of(ls.vb_steps) + pieces_of(ls.vb_ys) +
                  pieces_of(ls.vb_offs);
     }
+    for (TicketView &v : views)
+        if (v.status == SYMACCEL_OK) v.status = v.fmt_status;
     SYM_TRY(group_device(ctx, g, bound, n_allocs));
     const ListSizes ls = list_sizes(g);
     Block *blk = g->block;
@@ -1126,10 +1164,35 @@ int launch_group_inner(Lane *lane, Group *g, uint64_t *n_chunks, uint64_t *api_n
         *api_ns += ns_since(api0);
         // ---- scatter: PCM and the state after the batch back into the submissions' slots
         BatchCopyDesc *s0 = w;
+        bool converting = false;
+        const size_t plane_pitch = g->row_pitch ? g->row_pitch : (ps.in_place ? ps.in[0] : ps.out);  // bytes between the chains of d_out
         for (size_t ti = t0; ti < t1; ++ti) {
             const TicketView &t = views[ti];
             const SlotLayout l = slot_layout(ps, t.n_chains);
-            if (g->kind == SYMACCEL_BATCH_VORBIS_SYNTH || g->kind == SYMACCEL_BATCH_VORBIS_DECODE) {
+            if (t.out_fmt) {
+                // converted and interleaved on the way out: one piece per frame range of an interleave group, the groups packed behind
+                // each other at the front of slot.out (a submission that failed gets no PCM: nothing of it is valid)
+                const unsigned sb = (unsigned)symaccel_sample_bytes(t.out_fmt), tile = pcm_tile_frames(t.channels, sb);
+                const size_t fb = (size_t)t.channels * sb;
+                char *dst = t.slot + l.out;
+                for (size_t c = 0; t.status == SYMACCEL_OK && c < t.n_chains; c += t.channels) {
+                    size_t lines, samples = native_samples;
+                    if (vorbis_kind)
+                        vorbis_used(reinterpret_cast<const uint8_t *>(t.slot + l.in[1]) + c * g->units, g->units,
+                                    reinterpret_cast<const int32_t *>(t.slot + l.state[0])[c], g->param & 255, (g->param >> 8) & 255, &lines, &samples);
+                    const char *src = g->d_out + ((size_t)t.first_chain + c) * plane_pitch;
+                    for (size_t f0 = 0; f0 < samples; f0 += tile) {
+                        const size_t nf = std::min<size_t>(tile, samples - f0);
+                        w->src = src + f0 * 4;
+                        w->dst = dst + f0 * fb;
+                        w->bytes = (uint32_t)(nf * fb);
+                        w->pad = kBatchPieceConvert | (serial_kind(g->kind) ? kBatchPieceFromI32 : 0u) | ((uint32_t)nf << 12) | (t.channels << 8) | (uint32_t)t.out_fmt;
+                        ++w;
+                    }
+                    dst += samples * fb;
+                    converting = true;
+                }
+            } else if (g->kind == SYMACCEL_BATCH_VORBIS_SYNTH || g->kind == SYMACCEL_BATCH_VORBIS_DECODE) {
                 // (the state planes of the slot still hold the state BEFORE the batch here: the scatter that overwrites them is the
                 // one being built)
                 for (size_t c = 0; c < t.n_chains; ++c) {
@@ -1155,7 +1218,7 @@ int launch_group_inner(Lane *lane, Group *g, uint64_t *n_chunks, uint64_t *api_n
         }
         for (const Dma &m : dma) SYM_GPU(ctx, hipMemcpyAsync(m.dst, m.src, m.bytes, hipMemcpyDeviceToHost, s_out));
         dma.clear();
-        SYM_TRY(launch_batch_copy(ctx, s_out, s0, (size_t)(w - s0), true));
+        SYM_TRY(launch_batch_copy(ctx, s_out, s0, (size_t)(w - s0), true, converting ? plane_pitch / 4 : 0));
         *api_ns += ns_since(api1);
         *n_chunks += 1;
         t0 = t1;
@@ -1246,7 +1309,7 @@ void flush_group(symaccel_batcher *b, Group *g, std::unique_lock<std::mutex> &lo
         const Clock::time_point closing = Clock::now();
         for (size_t i = 0; i < g->tickets; ++i) {
             const Ticket &t = b->tickets[g->ticket_ids[i]];
-            g->views[i] = TicketView{t.slot, t.first_chain, t.n_chains, SYMACCEL_OK};
+            g->views[i] = TicketView{t.slot, t.first_chain, t.n_chains, SYMACCEL_OK, t.out_fmt, t.channels, 0};
             if (t.committed_at != Clock::time_point{}) b->stats.commit_to_launch_ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(closing - t.committed_at).count();
         }
         if (g->kind == SYMACCEL_BATCH_AAC_DECODE && g->param >= 0) g->aac_maps = b->bands[(size_t)g->param].maps;  // (the index was checked by reserve())
@@ -1294,6 +1357,7 @@ void flush_group(symaccel_batcher *b, Group *g, std::unique_lock<std::mutex> &lo
         for (size_t i = 0; i < g->tickets; ++i) {
             Ticket &t = b->tickets[g->ticket_ids[i]];
             t.status = st != SYMACCEL_OK ? st : g->views[i].status;
+            if (t.out_fmt) t.out_valid = t.status == SYMACCEL_OK ? g->views[i].out_valid : 0;
             if (t.status != SYMACCEL_OK) b->stats.failed_tickets += 1;
         }
     }
@@ -1366,7 +1430,7 @@ void fill_slot(const Group *g, const Ticket *t, symaccel_batch_slot *slot) {
         slot->state_bytes[i] = l.state_bytes[i];
     }
     slot->out = t->slot + l.out;
-    slot->out_bytes = l.out_bytes;
+    slot->out_bytes = t->out_fmt ? t->out_valid : l.out_bytes;
 }
 
 // Wait until nothing of a launched group is in flight (no mutex held).  The launch's last kernel writes the group's sequence number
@@ -1466,7 +1530,13 @@ int symaccel_batcher_destroy(symaccel_batcher *b) {
 
 int symaccel_batcher_reserve(symaccel_batcher *b, int kind, int param, size_t n_chains, size_t units_per_chain, symaccel_batch_slot *slot,
                              uint64_t *ticket) {
+    return symaccel_batcher_reserve_fmt(b, kind, param, n_chains, units_per_chain, 0, 0, slot, ticket);
+}
+
+int symaccel_batcher_reserve_fmt(symaccel_batcher *b, int kind, int param, size_t n_chains, size_t units_per_chain, int out_fmt, int channels,
+                                 symaccel_batch_slot *slot, uint64_t *ticket) {
     if (!b || !slot || !ticket || n_chains == 0 || units_per_chain == 0 || n_chains > 0x7fffffffu) return SYMACCEL_ERR_INVALID_ARG;
+    if (out_fmt != 0 && (symaccel_sample_bytes(out_fmt) == 0 || channels < 1 || channels > 8 || n_chains % (size_t)channels != 0)) return SYMACCEL_ERR_INVALID_ARG;
     PlaneSizes ps;
     if (kind == SYMACCEL_BATCH_AAC_SYNTH) param = 0;
     if (!plane_sizes(kind, param, units_per_chain, &ps)) return SYMACCEL_ERR_INVALID_ARG;
@@ -1507,6 +1577,11 @@ int symaccel_batcher_reserve(symaccel_batcher *b, int kind, int param, size_t n_
     t->live = true;
     t->slot = mem;
     t->slot_bytes = cls;
+    if (out_fmt) {  // (the native planes are 4 bytes a sample: the region reserved for them holds any format)
+        t->out_fmt = out_fmt;
+        t->channels = (uint32_t)channels;
+        t->out_valid = lay.out_bytes / 4 * symaccel_sample_bytes(out_fmt);
+    }
     g->ticket_ids.push_back(idx);
     g->chains += n_chains;
     g->tickets += 1;
@@ -1660,6 +1735,11 @@ int symaccel_batcher_plane_bytes(int kind, int param, size_t units_per_chain, si
 
 int symaccel_batcher_submit(symaccel_batcher *b, int kind, int param, size_t n_chains, size_t units_per_chain, const void **in,
                             void **state_io, void *out, uint64_t *ticket) {
+    return symaccel_batcher_submit_fmt(b, kind, param, n_chains, units_per_chain, in, state_io, out, 0, 0, ticket);
+}
+
+int symaccel_batcher_submit_fmt(symaccel_batcher *b, int kind, int param, size_t n_chains, size_t units_per_chain, const void **in,
+                                void **state_io, void *out, int out_fmt, int channels, uint64_t *ticket) {
     if (!b || !in || !state_io || !out || !ticket) return SYMACCEL_ERR_INVALID_ARG;
     if (kind == SYMACCEL_BATCH_AAC_DECODE) return SYMACCEL_ERR_INVALID_ARG;  // (symaccel_batcher_submit_aac_decode writes the blob)
     PlaneSizes ps;
@@ -1670,7 +1750,7 @@ int symaccel_batcher_submit(symaccel_batcher *b, int kind, int param, size_t n_c
         if (!state_io[i]) return SYMACCEL_ERR_INVALID_ARG;
     symaccel_batch_slot slot;
     uint64_t id = 0;
-    SYM_TRY(symaccel_batcher_reserve(b, kind, param, n_chains, units_per_chain, &slot, &id));
+    SYM_TRY(symaccel_batcher_reserve_fmt(b, kind, param, n_chains, units_per_chain, out_fmt, channels, &slot, &id));
     for (int i = 0; i < ps.n_in; ++i) {
         if (in[i])
             std::memcpy(slot.input[i], in[i], slot.input_bytes[i]);

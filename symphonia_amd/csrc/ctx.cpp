@@ -1153,6 +1153,34 @@ int symaccel_flac_md5(symaccel_ctx *ctx, const int32_t *h_rows, size_t row_pitch
     return symaccel_sync(ctx);
 }
 
+// ---- PCM in the caller's sample format -------------------------------------------------------
+
+size_t symaccel_sample_bytes(int fmt) {
+    switch (fmt) {
+    case SYMACCEL_FMT_U8: case SYMACCEL_FMT_S8: return 1;
+    case SYMACCEL_FMT_U16: case SYMACCEL_FMT_S16: return 2;
+    case SYMACCEL_FMT_U24: case SYMACCEL_FMT_S24: return 3;
+    case SYMACCEL_FMT_U32: case SYMACCEL_FMT_S32: case SYMACCEL_FMT_F32: return 4;
+    default: return 0;
+    }
+}
+
+int symaccel_pcm_convert_device(symaccel_ctx *ctx, const void *d_src, int src_fmt, size_t plane_stride, size_t n_groups, size_t channels,
+                                size_t n_frames, void *d_dst, int dst_fmt, size_t dst_group_bytes) {
+    if (!ctx || !pcm_convert_shape_ok(src_fmt, plane_stride, n_groups, channels, n_frames, dst_fmt, dst_group_bytes)) return SYMACCEL_ERR_INVALID_ARG;
+    if (n_groups == 0 || n_frames == 0) return SYMACCEL_OK;
+    if (!d_src || !d_dst) return SYMACCEL_ERR_INVALID_ARG;
+    const size_t b = symaccel_sample_bytes(dst_fmt);
+    const uintptr_t s0 = (uintptr_t)d_src, t0 = (uintptr_t)d_dst;
+    if (s0 % 4 != 0 || ((b == 2 || b == 4) && t0 % b != 0)) return SYMACCEL_ERR_INVALID_ARG;
+    const size_t src_bytes = ((n_groups * channels - 1) * plane_stride + n_frames) * 4, dst_bytes = (n_groups - 1) * dst_group_bytes + n_frames * channels * b;
+    const bool in_place = channels == 1 && b == 4 && s0 == t0 && dst_group_bytes == plane_stride * 4;  // every sample is read and written by one lane
+    if (!in_place && s0 < t0 + dst_bytes && t0 < s0 + src_bytes) return SYMACCEL_ERR_INVALID_ARG;      // overlapping buffers
+    DeviceGuard dev(ctx);
+    if (!dev.ok()) return dev.status();
+    return launch_pcm_convert(ctx, ctx->stream, d_src, src_fmt, plane_stride, n_groups, channels, n_frames, d_dst, dst_fmt, dst_group_bytes);
+}
+
 // ---- per-record status arrays --------------------------------------------------------------
 
 int symaccel_flac_block_status_device(symaccel_ctx *ctx, const symaccel_flac_desc *d_desc, size_t n_blocks, size_t blocksize,

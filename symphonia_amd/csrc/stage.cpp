@@ -438,6 +438,52 @@ int symaccel_mp3_decode_pipelined(symaccel_ctx *ctx, const int16_t *h_quant, con
     return pp.drain();
 }
 
+// symaccel_pcm_convert_device between host buffers: chunks along the frame axis, like the synthesis entry points above.  A chunk's
+// planes sit back to back on the device at a pitch that is a multiple of 4 samples and its groups' outputs at a multiple of 16 bytes,
+// so that the kernel runs its aligned paths whatever the caller's strides are.
+int symaccel_pcm_convert(symaccel_ctx *ctx, const void *h_src, int src_fmt, size_t plane_stride, size_t n_groups, size_t channels,
+                         size_t n_frames, void *h_dst, int dst_fmt, size_t dst_group_bytes) {
+    if (!ctx || !pcm_convert_shape_ok(src_fmt, plane_stride, n_groups, channels, n_frames, dst_fmt, dst_group_bytes)) return SYMACCEL_ERR_INVALID_ARG;
+    if (n_groups == 0 || n_frames == 0) return SYMACCEL_OK;
+    if (!h_src || !h_dst) return SYMACCEL_ERR_INVALID_ARG;
+    const size_t b = symaccel_sample_bytes(dst_fmt), n_planes = n_groups * channels, frame_bytes = channels * b;
+    const uintptr_t s0 = (uintptr_t)h_src, t0 = (uintptr_t)h_dst;
+    const size_t src_bytes = ((n_planes - 1) * plane_stride + n_frames) * 4, dst_bytes = (n_groups - 1) * dst_group_bytes + n_frames * frame_bytes;
+    if (s0 < t0 + dst_bytes && t0 < s0 + src_bytes) return SYMACCEL_ERR_INVALID_ARG;  // overlapping buffers (the chunks of an in-place call would cross)
+    DeviceGuard dev(ctx);
+    if (!dev.ok()) return dev.status();
+    size_t cf = pick_chunk(n_frames, n_planes * 4, 0);
+    cf = std::min((cf + 3) & ~(size_t)3, (n_frames + 3) & ~(size_t)3);
+    const size_t d_group_bytes = (cf * frame_bytes + 15) & ~(size_t)15;
+    Pipe pp(ctx);
+    SYM_TRY(pp.init());
+    uint8_t *d_in[2], *d_out[2];
+    for (int k = 0; k < 2; ++k) {
+        SYM_TRY(pp.alloc((void **)&d_in[k], n_planes * cf * 4));
+        SYM_TRY(pp.alloc((void **)&d_out[k], n_groups * d_group_bytes));
+    }
+    SYM_TRY(pp.commit());
+    size_t k = 0;
+    for (size_t f0 = 0; f0 < n_frames; f0 += cf, ++k) {
+        const size_t nf = std::min(cf, n_frames - f0);
+        const int bi = (int)(k & 1);
+        if (k >= 2) {  // buffer set bi is free once chunk k-2's kernel has read its input and its output has left
+            SYM_GPU(ctx, hipStreamWaitEvent(pp.s_in, pp.ev_k[bi], 0));
+            SYM_GPU(ctx, hipStreamWaitEvent(ctx->stream, pp.ev_out[bi], 0));
+        }
+        SYM_TRY(copy_rows(ctx, d_in[bi], cf * 4, static_cast<const uint8_t *>(h_src) + f0 * 4, plane_stride * 4, nf * 4, n_planes, hipMemcpyHostToDevice, pp.s_in));
+        SYM_GPU(ctx, hipEventRecord(pp.ev_in[bi], pp.s_in));
+        SYM_GPU(ctx, hipStreamWaitEvent(ctx->stream, pp.ev_in[bi], 0));
+        SYM_TRY(launch_pcm_convert(ctx, ctx->stream, d_in[bi], src_fmt, cf, n_groups, channels, nf, d_out[bi], dst_fmt, d_group_bytes));
+        SYM_GPU(ctx, hipEventRecord(pp.ev_k[bi], ctx->stream));
+        SYM_GPU(ctx, hipStreamWaitEvent(pp.s_out, pp.ev_k[bi], 0));
+        SYM_TRY(copy_rows(ctx, static_cast<uint8_t *>(h_dst) + f0 * frame_bytes, dst_group_bytes, d_out[bi], d_group_bytes, nf * frame_bytes, n_groups,
+                          hipMemcpyDeviceToHost, pp.s_out));
+        SYM_GPU(ctx, hipEventRecord(pp.ev_out[bi], pp.s_out));
+    }
+    return pp.drain();
+}
+
 int symaccel_flac_restore_pipelined(symaccel_ctx *ctx, int32_t *h_buf, const symaccel_flac_desc *h_desc, const int32_t *h_coeffs,
                                     size_t n_blocks, size_t blocksize, size_t chunk_blocks) {
     if (!ctx || blocksize > 65535) return SYMACCEL_ERR_INVALID_ARG;

@@ -285,14 +285,38 @@ int launch_flac_restore(symaccel_ctx *ctx, int32_t *d_buf, const symaccel_flac_d
                         const int32_t *d_coeffs, size_t n_blocks, size_t blocksize, const uint8_t *d_pair_mode = nullptr,
                         uint32_t out_shift = 0, size_t stride = 0 /* words between rows; 0 = blocksize */);
 // batch_copy.hip: one piece (<= kBatchCopyPiece bytes) per workgroup, host (page-locked) <-> device in either direction
+// `pad` 0: copy `bytes` bytes.  Otherwise a CONVERTING piece of a scatter (a ticket with an output format): kBatchPieceConvert | kBatchPieceFromI32
+// (the planes hold i32, else f32) | frames << 12 (at most 4096) | channels << 8 | the destination SYMACCEL_FMT_*; src = the piece's first frame in the
+// first plane of its interleave group, the other planes launch_batch_copy's pcm_plane_stride samples apart; dst / bytes = its interleaved output
 struct BatchCopyDesc {
     const void *src;
     void *dst;
     uint32_t bytes, pad;
 };
 constexpr size_t kBatchCopyPiece = 16384;
-int launch_batch_copy(symaccel_ctx *ctx, hipStream_t stream, const BatchCopyDesc *descs, size_t n, bool scatter);
+constexpr uint32_t kBatchPieceConvert = 0x80000000u, kBatchPieceFromI32 = 0x10u;
+int launch_batch_copy(symaccel_ctx *ctx, hipStream_t stream, const BatchCopyDesc *descs, size_t n, bool scatter, size_t pcm_plane_stride = 0);
 int launch_batch_flag(symaccel_ctx *ctx, hipStream_t stream, uint64_t *h_flag, uint64_t seq);  // (h_flag: page-locked host memory)
+// pcm_convert.h works in tiles: a frame range of one interleave group whose output is contiguous and at most kPcmTileBytes long (the piece
+// size of the batcher's scatter).  Frames of a tile: a multiple of 16 (so every tile of a group starts at the group's alignment modulo 16
+// bytes), at most 4096.
+constexpr unsigned kPcmTileBytes = 16384;
+constexpr unsigned kPcmMaxChannels = 8;
+constexpr unsigned pcm_tile_frames(unsigned channels, unsigned sample_bytes) {
+    const unsigned f = (kPcmTileBytes / (channels * sample_bytes)) & ~15u;
+    return f > 4096u ? 4096u : f;
+}
+// batch_copy.hip: planes of F32 / S32 samples to interleaved samples of dst_fmt (pcm_convert.h); arguments as symaccel_pcm_convert_device, already checked
+int launch_pcm_convert(symaccel_ctx *ctx, hipStream_t stream, const void *d_src, int src_fmt, size_t plane_stride, size_t n_groups, size_t channels,
+                       size_t n_frames, void *d_dst, int dst_fmt, size_t dst_group_bytes);
+// what symaccel_pcm_convert(_device) refuse, pointers aside
+inline bool pcm_convert_shape_ok(int src_fmt, size_t plane_stride, size_t n_groups, size_t channels, size_t n_frames, int dst_fmt, size_t dst_group_bytes) {
+    const size_t b = symaccel_sample_bytes(dst_fmt);
+    if ((src_fmt != SYMACCEL_FMT_F32 && src_fmt != SYMACCEL_FMT_S32) || b == 0 || channels < 1 || channels > 8) return false;
+    if (n_frames > (size_t)1 << 36 || plane_stride > (size_t)1 << 36 || n_groups > (size_t)1 << 20 || dst_group_bytes > (size_t)1 << 40) return false;  // (keeps the extents in 64 bits)
+    if (plane_stride < n_frames || dst_group_bytes < n_frames * channels * b) return false;
+    return !((b == 2 || b == 4) && dst_group_bytes % b != 0);
+}
 int launch_probe_copy(symaccel_ctx *ctx, const void *d_src, void *d_dst, size_t bytes, unsigned frames_per_wavefront, unsigned flags);
 int launch_flac_decorrelate(symaccel_ctx *ctx, const uint8_t *d_mode, int32_t *d_ch0, int32_t *d_ch1,
                             size_t n_pairs, size_t blocksize, uint32_t out_shift);

@@ -9,7 +9,7 @@
 // peek that copies the next packet out of a small pool (a parser writes its output somewhere too).  Nothing here links the
 // oracle: bench.py times the CPU port beside this with its own harness.  One JSON line on stdout.
 //
-//   decoders_bench --codec aac|aacd|mp3|mp3h|vorbis|flac --streams S --lookahead L --packets P --threads T [--per-stream] [--direct] [--in-phase] [--flush-mb M] [--lanes N] [--via-registry]
+//   decoders_bench --codec aac|aacd|mp3|mp3h|vorbis|flac --streams S --lookahead L --packets P --threads T [--per-stream] [--direct] [--in-phase] [--flush-mb M] [--lanes N] [--via-registry] [--out-format f32|s16|s24|u8|f32i]
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -34,6 +34,18 @@ struct Args {
     std::string codec = "aac";
     size_t streams = 64, lookahead = 64, packets = 512, threads = 1, flush_mb = 0, warm = 0, lanes = 0;
     bool per_stream = false, direct = false, in_phase = false, via_registry = false;
+    // --out-format: what the decoders deliver.  f32 (the default) = the planes as they are (planar f32; FLAC: left-justified i32) -- the
+    // path without a conversion; s16 / s24 / u8 / f32i = interleaved samples of that format, converted in the batcher's scatter
+    // (LookaheadDecoder::set_output; f32i: f32, interleaved)
+    std::string out_format = "f32";
+    SampleFormat format() const {
+        if (out_format == "f32") return SampleFormat::Native;
+        if (out_format == "s16") return SampleFormat::S16;
+        if (out_format == "s24") return SampleFormat::S24;
+        if (out_format == "u8") return SampleFormat::U8;
+        if (out_format == "f32i") return SampleFormat::F32;
+        throw std::invalid_argument("--out-format: f32, s16, s24, u8 or f32i");
+    }
 };
 
 constexpr size_t kPool = 32;
@@ -282,6 +294,7 @@ int run(const Args &a, const char *codec_name, size_t frames_per_packet, size_t 
             st->dec.reset(new Decoder(*batcher, params<Codec>(), a.lookahead, peek));
         else
             st->dec.reset(new Decoder(ctx, params<Codec>(), a.lookahead, peek));
+        if (a.format() != SampleFormat::Native) st->dec->set_output(a.format(), true);  // (needs the batcher: throws with --per-stream)
     }
     std::mutex ctx_mu;  // per-stream mode: one context, externally synchronised
     std::atomic<size_t> failures{0};
@@ -289,6 +302,8 @@ int run(const Args &a, const char *codec_name, size_t frames_per_packet, size_t 
     // What decode() is handed: in the warm-up the parsed packet in full (a cold decoder transforms it at once); afterwards only its
     // identity -- the trait's packet carries the COMPRESSED bytes, and a packet the look-ahead has already parsed is not parsed
     // again (a decoder that did need the content here fails with "packet shape" and is counted in `failures`).
+    const bool converting = a.format() != SampleFormat::Native;
+    const size_t out_sample_bytes = converting ? sample_bytes(a.format()) : 4;
     auto phase = [&](size_t first, size_t count, bool full, bool lead) {
         std::vector<std::thread> ths;
         const size_t T = std::min(a.threads, a.streams);
@@ -307,9 +322,12 @@ int run(const Args &a, const char *codec_name, size_t frames_per_packet, size_t 
                             if (st.cursor <= i) st.cursor = i + 1;
                             if (batcher) {
                                 const auto &buf = st.dec->decode(p);
-                                uint32_t w;
-                                if (buf.frames) std::memcpy(&w, buf.planes[0] + (i % 1024 % buf.frames), 4);  // (touch the result)
-                                else w = 0;
+                                uint32_t w = 0;
+                                if (buf.frames && converting) {
+                                    const DecodedBytes &b = st.dec->last_decoded_bytes();
+                                    std::memcpy(&w, b.data + (i % 1024 % buf.frames) * (b.bytes / b.frames), std::min<size_t>(4, b.bytes / b.frames));  // (touch the result)
+                                } else if (buf.frames)
+                                    std::memcpy(&w, buf.planes[0] + (i % 1024 % buf.frames), 4);
                                 acc += w;
                             } else {
                                 std::lock_guard<std::mutex> lock(ctx_mu);
@@ -343,17 +361,17 @@ int run(const Args &a, const char *codec_name, size_t frames_per_packet, size_t 
                 "\"packets_per_s\": %.1f, \"frames_per_packet\": %zu, \"host_bytes_in_per_packet\": %zu, \"host_bytes_out_per_packet\": %zu, "
                 "\"GBps_each_way\": [%.3f, %.3f], \"decoder_batches\": %zu, \"launches\": %llu, \"kernel_launches\": %llu, \"max_chains_per_launch\": %llu, "
                 "\"staging_bytes\": %llu, \"staging_grew_bytes\": %llu, \"slots_peak\": [%llu, %llu], \"lanes\": %llu, \"mutex_wait_ms\": %.3f, \"mutex_contended\": %llu, \"launch_host_ms\": %.3f, \"launch_api_ms\": %.3f, \"lane_wait_ms\": %.3f, \"group_allocs\": %llu, \"blocks\": %llu, \"flag_wait_ms\": %.3f, \"commit_to_launch_ms_per_submission\": %.3f, \"waits\": %llu, \"waits_blocked\": %llu, \"launch_to_done_ms\": %.3f, "
-                "\"failed_tickets\": %llu, \"failures\": %zu, \"checksum\": %llu}\n",
+                "\"failed_tickets\": %llu, \"failures\": %zu, \"checksum\": %llu, \"out_format\": \"%s\", \"flag_wait_ns\": %llu}\n",
                 codec_name, a.via_registry ? "registry" : (batcher ? "batcher" : "per-stream"), a.direct ? "true" : "false", a.in_phase ? "true" : "false", a.streams, a.lookahead, std::min(a.threads, a.streams), n, secs, n / secs, frames_per_packet,
-                bytes_in_per_packet, frames_per_packet * params<Codec>().channels * 4, n * bytes_in_per_packet / secs / 1e9,
-                n * frames_per_packet * params<Codec>().channels * 4 / secs / 1e9, batches,
+                bytes_in_per_packet, frames_per_packet * params<Codec>().channels * out_sample_bytes, n * bytes_in_per_packet / secs / 1e9,
+                n * frames_per_packet * params<Codec>().channels * out_sample_bytes / secs / 1e9, batches,
                 (unsigned long long)(s1.launches - s0.launches), (unsigned long long)(s1.chunks - s0.chunks),
                 (unsigned long long)s1.max_chains_per_launch, (unsigned long long)s1.staging_bytes, (unsigned long long)(s1.staging_bytes - s0.staging_bytes), (unsigned long long)s0.slots_peak, (unsigned long long)s1.slots_peak, (unsigned long long)s1.lanes,
                 (double)(s1.mutex_wait_ns - s0.mutex_wait_ns) / 1e6, (unsigned long long)(s1.mutex_contended - s0.mutex_contended),
                 (double)(s1.launch_host_ns - s0.launch_host_ns) / 1e6, (double)(s1.launch_api_ns - s0.launch_api_ns) / 1e6,
                 (double)(s1.lane_wait_ns - s0.lane_wait_ns) / 1e6, (unsigned long long)(s1.group_allocs - s0.group_allocs), (unsigned long long)s1.blocks, (double)(s1.flag_wait_ns - s0.flag_wait_ns) / 1e6, (double)(s1.commit_to_launch_ns - s0.commit_to_launch_ns) / 1e6 / (double)std::max<uint64_t>(1, s1.submissions - s0.submissions), (unsigned long long)(s1.waits - s0.waits), (unsigned long long)(s1.waits_blocked - s0.waits_blocked), (double)(s1.launch_to_done_ns - s0.launch_to_done_ns) / 1e6 / (double)std::max<uint64_t>(1, s1.launches_timed - s0.launches_timed),
                 (unsigned long long)(s1.failed_tickets - s0.failed_tickets), failures.load(),
-                (unsigned long long)checksum.load());
+                (unsigned long long)checksum.load(), a.out_format.c_str(), (unsigned long long)(s1.flag_wait_ns - s0.flag_wait_ns));
     return failures.load() ? 1 : 0;
 }
 
@@ -376,6 +394,7 @@ int main(int argc, char **argv) {
         else if (k == "--direct") a.direct = true;
         else if (k == "--in-phase") a.in_phase = true;
         else if (k == "--via-registry") a.via_registry = true;
+        else if (k == "--out-format" && i + 1 < argc) a.out_format = argv[++i];
         else {
             std::fprintf(stderr, "unknown argument %s\n", k.c_str());
             return 2;

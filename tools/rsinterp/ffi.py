@@ -274,6 +274,19 @@ class Bridge:
                 self.word_fields[(base, fname)] = inner[1][-1]  # (u64 / i64 on the wire; `usize` to the crate)
         return np.dtype(fields)
 
+    def void_dtype(self, seq):
+        """a slice handed to a `*const c_void` / `*mut c_void` parameter (`planes.as_ptr() as *const c_void`): the C side sees the
+        elements' own bytes, so the layout is that of the values the slice holds (empty: bytes)"""
+        a, o, n = I.seq_view(I.deref(seq))
+        first = a[o] if n else None
+        if isinstance(first, I.Int) and first.t in SCALARS:
+            return np.dtype(SCALARS[first.t])
+        if isinstance(first, np.float32):
+            return np.dtype(np.float32)
+        if isinstance(first, float):
+            return np.dtype(np.float64)
+        return np.dtype(np.uint8)
+
     def field_dtype(self, fty):
         if fty[0] == 'tptr':  # an address (symaccel_batch_slot's planes)
             return (np.dtype(np.uint64),)
@@ -385,7 +398,7 @@ class Bridge:
             else:
                 if isinstance(x, RawMem):
                     x = I.Slice(x.arr.a, x.off, len(x.arr.a) - x.off, True)
-                dt = self.dtype(elem)
+                dt = self.void_dtype(x) if elem.split('::')[-1] == 'c_void' else self.dtype(elem)
                 arr = np.ascontiguousarray(self.to_np_seq(x, dt))
                 keep.append(arr)
                 cargs.append(arr.ctypes.data_as(C.c_void_p) if arr.size else None)

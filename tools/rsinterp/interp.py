@@ -2312,6 +2312,8 @@ class Interp:
         if name in ('format', 'concat', 'stringify', 'line', 'file', 'column'):
             return ''
         if name == 'cfg':  # no configuration flag is set here (not fuzzing, no debug assertions, no optional feature)
+            if len(toks) == 3 and toks[0].s == 'target_endian' and toks[1].s == '=':  # the hosts this project runs on are little-endian
+                return 'little' in toks[2].s
             return bool(toks) and toks[0].s == 'not'
         if name in self.macros:
             key = id(e)
@@ -2804,6 +2806,9 @@ class Interp:
                 return not np.signbit(x) if is32 else math.copysign(1.0, x) > 0
             if name == 'is_sign_negative':
                 return bool(np.signbit(x)) if is32 else math.copysign(1.0, x) < 0
+            if name in ('to_le_bytes', 'to_be_bytes', 'to_ne_bytes'):  # (the native order is little-endian here, as for the integers)
+                bs = F32(x).tobytes() if is32 else _struct.pack('<d', x)
+                return Arr([Int(b, 'u8') for b in (bs[::-1] if name == 'to_be_bytes' else bs)])
             if name == 'to_bits':
                 if is32:
                     return Int(int(F32(x).view(np.uint32)), 'u32')
