@@ -23,6 +23,7 @@
 //! (tests/test_{aac,mp3,vorbis,flac,alac}_packets.py).
 #![allow(clippy::needless_range_loop)]
 
+pub mod adpcm;
 mod aac;
 mod ctx;
 pub mod decoder;
@@ -37,6 +38,7 @@ mod pcm;
 mod vorbis;
 
 pub use aac::{AacFrontEnd, HipAacDecoder, ParsedAac};
+pub use adpcm::{AdpcmCodec, HipAdpcmDecoder};
 pub use alac::{AlacFrontEnd, HipAlacDecoder, ParsedAlac};
 pub use decoder::DecoderBatch;
 pub use ctx::{Context, Pinned, Pool};

@@ -729,6 +729,37 @@ int symaccel_pcm_convert_device(symaccel_ctx *ctx, const void *d_src, int src_fm
 int symaccel_pcm_convert(symaccel_ctx *ctx, const void *h_src, int src_fmt, size_t plane_stride, size_t n_groups, size_t channels,
                          size_t n_frames, void *h_dst, int dst_fmt, size_t dst_group_bytes);
 
+/* ------------------------------------------------------------------ ADPCM: packet bytes to PCM (csrc/adpcm.hip)
+ * symphonia-codec-adpcm (lib.rs:122-168): a packet is block_dur / frames_per_block blocks back to back, every block carries its own
+ * predictor state (reset() is empty, lib.rs:217-219), and block k's frames land at [k * fpb, (k + 1) * fpb) of each channel's plane.
+ * There is nothing for a host front end to do: the bytes go up the link and PCM comes down.  The codecs: MS (codec_ms.rs), IMA WAV
+ * (codec_ima_wav.rs), IMA QT (codec_ima_qt.rs); mono and stereo.  Bit for bit the reference's release build, the i32 wrapping of the MS
+ * delta recurrence on arbitrary bytes included. */
+#define SYMACCEL_ADPCM_MS 1      /* CODEC_ID_ADPCM_MS:      lib.rs:109, codec_ms.rs */
+#define SYMACCEL_ADPCM_IMA_WAV 2 /* CODEC_ID_ADPCM_IMA_WAV: lib.rs:110, codec_ima_wav.rs */
+#define SYMACCEL_ADPCM_IMA_QT 3  /* CODEC_ID_ADPCM_IMA_QT:  lib.rs:111, codec_ima_qt.rs */
+/* Bytes of one block: MS 6 + fpb / 2 (mono), 12 + fpb (stereo); IMA WAV 4 + (fpb - 1) / 2, 7 + fpb; IMA QT 34 * channels.  0 for an
+ * unknown codec and for the shapes the device decoder refuses -- those where the reference leaves samples of its buffer unwritten or
+ * indexes out of range, which belong to the decoder below: MS with fpb < 2 or a mono block of odd fpb (codec_ms.rs:107-113), IMA WAV
+ * mono of even fpb (codec_ima_wav.rs:32-39), IMA WAV stereo unless (fpb - 1) % 8 == 0 (rejected at :46-48), IMA QT with fpb != 64
+ * (codec_ima_qt.rs:29-36), channels other than 1 and 2 (lib.rs:97-99), fpb above 2^20.  Pure arithmetic, no context. */
+size_t symaccel_adpcm_block_bytes(int codec, size_t channels, size_t frames_per_block);
+/* n_blocks blocks, block k at d_bytes + k * block_pitch (block_pitch >= the block's bytes, at most 2^24; any alignment -- a pitch and
+ * a base that are multiples of 16 load fastest).  out_fmt 0: d_pcm[n_blocks][channels][frames_per_block] int32, left-justified (every
+ * sample is an i16 << 16: from_i16_shift, common.rs:29-33), 4-byte aligned.  out_fmt SYMACCEL_FMT_*: d_pcm[n_blocks][frames_per_block]
+ * [channels] samples of that format, what symaccel_pcm_convert_device makes of the native planes with a block as the interleave group
+ * (S16 is lossless); aligned to the sample size for the 2- and 4-byte formats.  d_status[n_blocks] (uint8, may be NULL): 0, 1 = MS block
+ * predictor above 6 (Error::Unsupported, codec_ms.rs:25-29), 2 = IMA WAV step index above 88 (Error::DecodeError, codec_ima_wav.rs:17-19);
+ * such a block decodes to silence (the native 0 in out_fmt) and its neighbours are untouched.  Input and output must not overlap.
+ * SYMACCEL_ERR_UNSUPPORTED for a shape symaccel_adpcm_block_bytes refuses, SYMACCEL_ERR_INVALID_ARG for anything else that is wrong;
+ * both before anything is launched. */
+int symaccel_adpcm_decode_device(symaccel_ctx *ctx, const void *d_bytes, size_t block_pitch, size_t n_blocks, int codec, size_t channels,
+                                 size_t frames_per_block, void *d_pcm, int out_fmt, uint8_t *d_status);
+/* The same between host buffers (h_status may be NULL), staged through page-locked memory in chunks of whole blocks, copy-in, kernel
+ * and copy-out overlapped: one byte up the link, two samples down. */
+int symaccel_adpcm_decode(symaccel_ctx *ctx, const void *h_bytes, size_t block_pitch, size_t n_blocks, int codec, size_t channels,
+                          size_t frames_per_block, void *h_pcm, int out_fmt, uint8_t *h_status);
+
 /* ------------------------------------------------------------------ cross-stream batcher (csrc/batcher.cpp)
  * AudioDecoder::decode_ref (symphonia-core/src/codecs/audio.rs:279-297) sees one packet of one track and the registry builds
  * every decoder from (params, opts) alone (codecs/registry.rs:330-341): a decoder cannot see its siblings, so N decoders
@@ -782,7 +813,18 @@ int symaccel_pcm_convert(symaccel_ctx *ctx, const void *h_src, int src_fmt, size
  *   SYMACCEL_BATCH_ALAC_PREDICT symaccel_alac_predict across streams, the same shape: in = { buf[chain][unit] i32 (in place), desc[chain]
  *                              (symaccel_alac_desc), coeffs[chain][32] }; param = 0.  With param = 0x100: in[3] = pair_weight[chain / 2] i32,
  *                              in[4] = pair_shift[chain / 2] u8 (symaccel_alac_predict_stereo_device, lib.rs:541-560)
- * `units_per_chain` = frames (AAC) / granules (MP3) / blocks (Vorbis) / words (FLAC, ALAC) per chain.  Two forms:
+ *   SYMACCEL_BATCH_ADPCM_DECODE symaccel_adpcm_decode across streams (symphonia-codec-adpcm lib.rs:122-168): a chain is ONE BLOCK, units_per_chain
+ *                              = the block's bytes, so the packets of every stream of one codec, channel count and block size share a
+ *                              launch: in = { bytes[chain][unit] u8 }; no state; out = pcm[chain][channel][fpb] i32, left-justified; param =
+ *                              codec | channels << 8.  fpb follows from the byte count (symaccel_adpcm_block_bytes read backwards); a count no
+ *                              accepted shape has is SYMACCEL_ERR_INVALID_ARG from reserve().  A submission holding a block the reference
+ *                              rejects fails alone with the status of its first such block: SYMACCEL_ERR_UNSUPPORTED (MS block predictor,
+ *                              codec_ms.rs:25-29) or SYMACCEL_ERR_DECODE (IMA WAV step index, codec_ima_wav.rs:17-19).  The batcher reads
+ *                              the preambles in the page-locked slot when the group is launched (check_adpcm, csrc/batcher.cpp) instead of
+ *                              bringing the kernel's status bytes back: the two rules -- byte k of an MS block above 6, byte 4 k + 2 of an
+ *                              IMA WAV block above 88, per channel k -- are stated there and in csrc/adpcm.hip and must stay in step
+ *                              (tests/test_batcher_adpcm.py compares the ticket's status with the kernel's)
+ * `units_per_chain` = frames (AAC) / granules (MP3) / blocks (Vorbis) / words (FLAC, ALAC) / bytes (ADPCM) per chain.  Two forms:
  *   zero-copy:  reserve() hands out a slot of page-locked staging memory (the front end writes its output straight into the DMA
  *               source), commit() says it is filled, wait() blocks until slot.out / slot.state hold the PCM and the state AFTER
  *               the batch, release() gives the slot back.  Commit a reservation before waiting for anything on the same thread.
@@ -804,6 +846,7 @@ int symaccel_pcm_convert(symaccel_ctx *ctx, const void *h_src, int src_fmt, size
 #define SYMACCEL_BATCH_VORBIS_DECODE 6
 #define SYMACCEL_BATCH_FLAC_RESTORE 7
 #define SYMACCEL_BATCH_ALAC_PREDICT 8
+#define SYMACCEL_BATCH_ADPCM_DECODE 9
 #define SYMACCEL_BATCH_MAX_INPUTS 6
 typedef struct symaccel_batcher symaccel_batcher;
 typedef struct symaccel_batch_slot {
@@ -867,7 +910,10 @@ int symaccel_batcher_submit(symaccel_batcher *b, int kind, int param, size_t n_c
  * block writes) are counted in samples_per_chain and hold nothing defined -- here the conversion of device memory nobody wrote.  slot.out_bytes is the number of valid bytes: after wait()
  * what was written (0 for a submission that failed), at reserve() the most the shape can give (for Vorbis the count is not known before
  * the flags are written).  collect() copies exactly slot.out_bytes bytes to `out`.  State planes are never converted.  Submissions of
- * any formats and groupings share the groups and launches of their (kind, param, units_per_chain). */
+ * any formats and groupings share the groups and launches of their (kind, param, units_per_chain).
+ * ADPCM_DECODE differs in two ways: the interleave group is ONE BLOCK's channels (channels must equal the count in param, n_chains is any
+ * number of blocks; the output is [n_chains][fpb][channels] samples, S16 being lossless), and the decode kernel writes the format itself,
+ * so submissions of different formats go to different launches. */
 int symaccel_batcher_reserve_fmt(symaccel_batcher *b, int kind, int param, size_t n_chains, size_t units_per_chain, int out_fmt,
                                  int channels, symaccel_batch_slot *slot, uint64_t *ticket);
 int symaccel_batcher_submit_fmt(symaccel_batcher *b, int kind, int param, size_t n_chains, size_t units_per_chain, const void **input,
@@ -911,6 +957,10 @@ int symaccel_batcher_submit_flac_restore(symaccel_batcher *b, int32_t *buf_io, c
 int symaccel_batcher_submit_alac_predict(symaccel_batcher *b, int32_t *buf_io, const symaccel_alac_desc *desc, const int32_t *coeffs,
                                          const int32_t *pair_weight, const uint8_t *pair_shift, size_t n_blocks, size_t blocksize,
                                          uint64_t *ticket);
+/* symaccel_adpcm_decode for the blocks of one packet (or of several): bytes[n_blocks][block_bytes], pcm[n_blocks][channels][fpb] written by
+ * collect(); submit_fmt() with SYMACCEL_BATCH_ADPCM_DECODE delivers another format */
+int symaccel_batcher_submit_adpcm_decode(symaccel_batcher *b, const uint8_t *bytes, int codec, size_t channels, size_t n_blocks,
+                                         size_t block_bytes, int32_t *pcm, uint64_t *ticket);
 /* wait + copy the PCM and the state after the batch into the `*_io` / `pcm` pointers given to submit + release */
 int symaccel_batcher_collect(symaccel_batcher *b, uint64_t ticket);
 /* give up a submission (seek, reset): wait until nothing of it is in flight, write nothing, release */

@@ -100,6 +100,13 @@ public:
                      SampleFormat dst, std::size_t dst_group_bytes) {
         check(symaccel_pcm_convert(ctx_, h_src, static_cast<int>(src), plane_stride, n_groups, channels, n_frames, h_dst, static_cast<int>(dst), dst_group_bytes), ctx_);
     }
+    // symphonia-codec-adpcm's block decoders (codec_ms.rs, codec_ima_wav.rs, codec_ima_qt.rs) for n_blocks blocks in host memory,
+    // block_pitch bytes apart: h_pcm[n_blocks][channels][frames_per_block] i32 (Native), or [n_blocks][frames_per_block][channels] samples
+    // of `out`; h_status[n_blocks] (may be null): 0, 1 = MS block predictor out of range, 2 = IMA WAV step index out of range
+    void adpcm_decode(const void *h_bytes, std::size_t block_pitch, std::size_t n_blocks, int codec, std::size_t channels, std::size_t frames_per_block, void *h_pcm,
+                      SampleFormat out = SampleFormat::Native, std::uint8_t *h_status = nullptr) {
+        check(symaccel_adpcm_decode(ctx_, h_bytes, block_pitch, n_blocks, codec, channels, frames_per_block, h_pcm, static_cast<int>(out), h_status), ctx_);
+    }
 
 private:
     symaccel_ctx *ctx_ = nullptr;
@@ -554,6 +561,21 @@ struct DecodedBytes {
     std::size_t plane_stride = 0;  // bytes between the channels of a planar result; 0 = interleaved
 };
 
+// A codec whose batcher kind delivers a format as [block][frame][channel] (ADPCM: the interleave group is one block's channels, the blocks
+// of a packet follow one another) says so with `kBlockInterleave`: publish() then finds a packet's bytes at its first block
+template <class C, class = void>
+struct has_block_interleave : std::false_type {};
+template <class C>
+struct has_block_interleave<C, std::void_t<decltype(C::kBlockInterleave)>> : std::true_type {};
+
+// A codec with no host parse stage (ADPCM) finds a packet's own errors -- a rejected preamble, a packet shorter than its blocks -- when the
+// batch is assembled.  It keeps them per packet (`packet_error(i)`), the packet runs as silence, and decode() throws the error when THAT
+// packet's turn comes: a packet fails alone (codecs/audio.rs:273-278), its neighbours in the look-ahead batch keep their PCM.
+template <class C, class = void>
+struct has_packet_errors : std::false_type {};
+template <class C>
+struct has_packet_errors<C, std::void_t<decltype(std::declval<const C &>().packet_error(std::size_t{}))>> : std::true_type {};
+
 struct FinalizeResult {  // codecs/audio.rs:230-236
     std::optional<bool> verify_ok;
 };
@@ -641,6 +663,14 @@ public:
                 throw;
             }
         }
+        if constexpr (has_packet_errors<Codec>::value) {
+            if (const Error *e = codec_.packet_error(head_)) {
+                const Error own = *e;
+                ++head_;       // the packet is consumed: the rest of the batch stays
+                clear_last();  // audio.rs:278
+                throw own;
+            }
+        }
         publish(head_++);
         last_packet_ = packet;
         have_last_packet_ = true;
@@ -669,8 +699,10 @@ public:
             if (!batcher_ || Codec::kBatchKind == 0) throw std::invalid_argument("LookaheadDecoder::set_output: the conversion happens in the batcher's scatter");
             if (sample_bytes(format) == 0 || codec_.channels() > 8) throw std::invalid_argument("LookaheadDecoder::set_output: format / channels");
             if (!codec_.device_output_is_final()) throw Error(Error::Kind::Unsupported, SYMACCEL_ERR_UNSUPPORTED, "set_output: this stream's planes are finished on the host");
+            if (has_block_interleave<Codec>::value && !interleaved) throw Error(Error::Kind::Unsupported, SYMACCEL_ERR_UNSUPPORTED, "set_output: this codec's kernel writes interleaved frames");
         }
         if (cur_live_ || next_live_ || head_ < ready_.size()) throw std::logic_error("LookaheadDecoder::set_output: between batches only (before decode() or after reset())");
+        if constexpr (has_block_interleave<Codec>::value) codec_.set_output_format(format);
         out_fmt_ = format;
         out_interleaved_ = interleaved;
         clear_last();
@@ -887,7 +919,11 @@ private:
                 bytes_.frames = last_.frames;
                 bytes_.channels = nch;
                 bytes_.format = out_fmt_;
-                if (out_interleaved_) {
+                if constexpr (has_block_interleave<Codec>::value) {
+                    bytes_.data = out_base_ + at0 * sb;  // (plane_offset(0, i) = the samples in front of the packet's first block, all channels)
+                    bytes_.bytes = last_.frames * nch * sb;
+                    bytes_.plane_stride = 0;
+                } else if (out_interleaved_) {
                     bytes_.data = out_base_ + ((at0 / native / nch) * per_chain + at0 % native) * nch * sb;
                     bytes_.bytes = last_.frames * nch * sb;
                     bytes_.plane_stride = 0;
@@ -1638,6 +1674,131 @@ private:
     std::vector<std::uint8_t> modes_;
 };
 
+// ADPCM (symphonia-codec-adpcm): MS, IMA WAV, IMA QT; mono and stereo.  A packet is block_dur / frames_per_block blocks back to back
+// (lib.rs:122-168) and there is NO CPU side: the packet's bytes go up as they are, the whole numeric decode runs on the device
+// (csrc/adpcm.hip).  Nothing is carried from packet to packet (lib.rs:217-219), so reset() has nothing to zero and a skipped packet needs
+// no replay.  With the batcher (SYMACCEL_BATCH_ADPCM_DECODE) a chain is ONE BLOCK and every packet gets `max_frames_per_packet /
+// frames_per_block` chains (a shorter last packet leaves zero blocks behind it, never published), so the packets of every stream of one
+// codec, channel count and block size share launches.  The device writes pcm[block][channel][fpb]; the trait's planes are
+// [channel][block * fpb + frame], so a stereo packet of several blocks is re-packed in the slot on the host (take_state).  A delivered
+// format needs no re-pack: the kernel writes [block][frame][channel] and a packet's blocks follow one another.
+struct Adpcm {
+    using Sample = std::int32_t;
+    struct Params {
+        int codec = SYMACCEL_ADPCM_MS;  // SYMACCEL_ADPCM_*
+        std::size_t channels = 2;
+        std::size_t frames_per_block = 0;       // AudioCodecParameters::frames_per_block (lib.rs:84-86)
+        std::size_t max_frames_per_packet = 0;  // ... ::max_frames_per_packet (lib.rs:79-82)
+    };
+    struct Packet {
+        std::uint64_t ts = 0;
+        std::size_t block_dur = 0;         // frames (packet.block_dur(), lib.rs:131)
+        std::vector<std::uint8_t> data;    // at least block_dur / frames_per_block blocks; what follows them is ignored, as in the reference
+    };
+    // Error{Unsupported} for the shapes the device decoder leaves to the decoder below (symaccel_adpcm_block_bytes == 0)
+    explicit Adpcm(const Params &p)
+        : codec_(p.codec), nch_(p.channels), fpb_(p.frames_per_block), bytes_(symaccel_adpcm_block_bytes(p.codec, p.channels, p.frames_per_block)),
+          bpp_(p.frames_per_block ? p.max_frames_per_packet / p.frames_per_block : 0) {
+        if (bytes_ == 0) throw Error(Error::Kind::Unsupported, SYMACCEL_ERR_UNSUPPORTED, "adpcm: a shape the device decoder refuses");
+        if (bpp_ == 0) throw Error(Error::Kind::Unsupported, SYMACCEL_ERR_UNSUPPORTED, "adpcm: maximum frames per packet is required");
+    }
+    static constexpr int kBatchKind = SYMACCEL_BATCH_ADPCM_DECODE;
+    static constexpr bool kDirect = false;
+    static constexpr bool kBlockInterleave = true;
+    struct BatchView {};
+    void attach(Batcher &) {}
+    void set_output_format(SampleFormat f) { native_ = f == SampleFormat::Native; }
+    int batch_param() const { return codec_ | (int)(nch_ << 8); }
+    std::size_t batch_chains(std::size_t k) const { return k * bpp_; }
+    std::size_t batch_units(std::size_t) const { return bytes_; }
+    std::size_t block_bytes() const { return bytes_; }
+    // The packet's block count, and what the reference's readers would make of it, in their order (lib.rs:131-165 over io/buf_reader.rs):
+    // block after block, the preamble bytes as they are read -- an MS block predictor above 6 is Unsupported (codec_ms.rs:25-29, 47-63), an
+    // IMA WAV step index above 88 a DecodeError (codec_ima_wav.rs:14-25; the C++ Error has no such kind: Kind::IoError carrying the status
+    // SYMACCEL_ERR_DECODE is how this header spells it, as check() does) --, a read past the end of the packet the I/O error of BufReader.
+    std::size_t inspect(const Packet &p, std::optional<Error> *err) const {
+        const std::size_t n = p.block_dur / fpb_;
+        if (n > bpp_) throw std::invalid_argument("Adpcm: a packet longer than max_frames_per_packet");
+        err->reset();
+        for (std::size_t j = 0; j < n && !*err; ++j) {
+            const std::size_t at = j * bytes_, left = p.data.size() > at ? p.data.size() - at : 0;
+            const std::uint8_t *b = p.data.data() + at;
+            for (std::size_t c = 0; c < nch_ && !*err; ++c) {
+                if (codec_ == SYMACCEL_ADPCM_MS) {
+                    if (left <= c) err->emplace(Error::Kind::IoError, SYMACCEL_ERR_DEVICE, "adpcm: buffer underrun");
+                    else if (b[c] > 6) err->emplace(Error::Kind::Unsupported, SYMACCEL_ERR_UNSUPPORTED, "adpcm: block predictor exceeds range");
+                } else if (codec_ == SYMACCEL_ADPCM_IMA_WAV) {
+                    if (left < 4 * c + 3) err->emplace(Error::Kind::IoError, SYMACCEL_ERR_DEVICE, "adpcm: buffer underrun");
+                    else if (b[4 * c + 2] > 88) err->emplace(Error::Kind::IoError, SYMACCEL_ERR_DECODE, "adpcm (ima): invalid step index");
+                    else if (left < 4 * c + 4) err->emplace(Error::Kind::IoError, SYMACCEL_ERR_DEVICE, "adpcm: buffer underrun");
+                }
+            }
+            if (!*err && left < bytes_) err->emplace(Error::Kind::IoError, SYMACCEL_ERR_DEVICE, "adpcm: buffer underrun");
+        }
+        return n;
+    }
+    const Error *packet_error(std::size_t i) const { return i < errors_.size() && errors_[i] ? &*errors_[i] : nullptr; }
+    // packet i's blocks into `rows` (bpp slots of it): a packet with an error of its own, and the slots behind a short packet, run as zero
+    // blocks (an accepted preamble, silence), which nobody is shown
+    std::size_t place(const Packet &p, std::uint8_t *rows, std::size_t slots, std::optional<Error> *err) const {
+        const std::size_t n = inspect(p, err), good = *err ? 0 : n;
+        std::copy_n(p.data.data(), good * bytes_, rows);
+        std::fill(rows + good * bytes_, rows + slots * bytes_, 0);
+        return n;
+    }
+    void fill_slot(const std::vector<Packet> &batch, const symaccel_batch_slot &slot) {
+        std::uint8_t *rows = static_cast<std::uint8_t *>(slot.input[0]);
+        next_blocks_.assign(batch.size(), 0);
+        next_errors_.assign(batch.size(), std::nullopt);
+        for (std::size_t i = 0; i < batch.size(); ++i) next_blocks_[i] = place(batch[i], rows + i * bpp_ * bytes_, bpp_, &next_errors_[i]);
+    }
+    void take_state(const symaccel_batch_slot &slot) {
+        blocks_.swap(next_blocks_);
+        errors_.swap(next_errors_);
+        stride_ = bpp_;
+        if (native_ && nch_ == 2 && bpp_ > 1) repack(static_cast<std::int32_t *>(slot.out), blocks_.size(), bpp_);
+    }
+    static std::uint64_t id(const Packet &p) { return p.ts; }
+    std::size_t channels() const { return nch_; }
+    bool device_output_is_final() const { return true; }
+    std::size_t packet_frames(std::size_t i) const { return blocks_[i] * fpb_; }
+    // native: packet i's channel c is [block * fpb + frame] at (i * nch + c) * stride * fpb; a format: channel 0 names the packet's first sample
+    std::size_t plane_offset(std::size_t c, std::size_t i, std::size_t) const { return (i * nch_ + (native_ ? c : 0)) * stride_ * fpb_; }
+    void reset_state() {}
+    void decode_batch(Context &ctx, const std::vector<Packet> &batch, std::vector<std::int32_t> &pcm) {
+        const std::size_t k = batch.size();
+        blocks_.assign(k, 0);
+        errors_.assign(k, std::nullopt);
+        stride_ = bpp_;
+        rows_.assign(k * stride_ * bytes_, 0);
+        for (std::size_t i = 0; i < k; ++i) blocks_[i] = place(batch[i], rows_.data() + i * stride_ * bytes_, stride_, &errors_[i]);
+        pcm.assign(k * stride_ * nch_ * fpb_, 0);
+        if (k * stride_ == 0) return;
+        ctx.adpcm_decode(rows_.data(), bytes_, k * stride_, codec_, nch_, fpb_, pcm.data(), SampleFormat::Native, nullptr);
+        if (nch_ == 2 && stride_ > 1) repack(pcm.data(), k, stride_);
+    }
+
+private:
+    // [packet][block][channel][fpb] -> [packet][channel][block][fpb], packet by packet
+    void repack(std::int32_t *pcm, std::size_t k, std::size_t blocks) {
+        tmp_.resize(blocks * nch_ * fpb_);
+        for (std::size_t i = 0; i < k; ++i) {
+            std::int32_t *p = pcm + i * blocks * nch_ * fpb_;
+            std::copy_n(p, tmp_.size(), tmp_.data());
+            for (std::size_t c = 0; c < nch_; ++c)
+                for (std::size_t j = 0; j < blocks; ++j) std::copy_n(tmp_.data() + (j * nch_ + c) * fpb_, fpb_, p + (c * blocks + j) * fpb_);
+        }
+    }
+    int codec_;
+    std::size_t nch_, fpb_, bytes_, bpp_;
+    std::size_t stride_ = 0;  // blocks every packet of the current batch occupies
+    bool native_ = true;
+    std::vector<std::size_t> blocks_, next_blocks_;
+    std::vector<std::optional<Error>> errors_, next_errors_;  // per packet of the batch: what decode() throws when its turn comes
+    std::vector<std::uint8_t> rows_;
+    std::vector<std::int32_t> tmp_;
+};
+
 // CodecRegistry (symphonia-core/src/codecs/registry.rs:220-341).  The reference's registry maps a codec id to a factory that is handed
 // (params, options) and NOTHING ELSE -- `RegisterableAudioDecoder::try_registry_new` (registry.rs:34-44) -- so a decoder it builds cannot
 // be told about its siblings: the factories here find the process-wide batcher themselves (`Batcher::shared()`), exactly as the Rust shim's
@@ -1690,6 +1851,8 @@ inline void register_enabled_codecs(CodecRegistry &registry) {
     registry.register_audio_decoder<Vorbis>();
     registry.register_audio_decoder<Flac>();
 }
+// ... and ADPCM, entered by a call of its own (the shim's `adpcm::register`): the list above is the one the shim's `register()` has
+inline void register_adpcm(CodecRegistry &registry) { registry.register_audio_decoder<Adpcm>(); }
 
 }  // namespace codecs
 

@@ -28,6 +28,9 @@ TABLE_MP3_POW43, TABLE_MP3_POW2AB = 8, 9
 # SYMACCEL_FMT_*: the sample formats PCM can be delivered in (symaccel_pcm_convert)
 FMT_U8, FMT_S8, FMT_U16, FMT_S16, FMT_U24, FMT_S24, FMT_U32, FMT_S32, FMT_F32 = range(1, 10)
 
+# SYMACCEL_ADPCM_*: the codecs of symaccel_adpcm_decode
+ADPCM_MS, ADPCM_IMA_WAV, ADPCM_IMA_QT = 1, 2, 3
+
 # every symbol include/symaccel.h declares (tests/test_abi.py checks the built library exports all)
 ABI_SYMBOLS = [
     "symaccel_abi_version", "symaccel_strerror", "symaccel_last_error", "symaccel_ctx_create",
@@ -61,6 +64,8 @@ ABI_SYMBOLS = [
     "symaccel_md5_init", "symaccel_md5_update", "symaccel_md5_digest", "symaccel_flac_md5_device", "symaccel_flac_md5",
     "symaccel_sample_bytes", "symaccel_pcm_convert_device", "symaccel_pcm_convert",
     "symaccel_batcher_reserve_fmt", "symaccel_batcher_submit_fmt",
+    "symaccel_adpcm_block_bytes", "symaccel_adpcm_decode_device", "symaccel_adpcm_decode",
+    "symaccel_batcher_submit_adpcm_decode",
 ]
 
 _vp, _sz, _i, _d, _u32 = C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.c_uint32
@@ -165,6 +170,7 @@ class Library:
         d.symaccel_batcher_submit_vorbis_decode.argtypes = [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, C.POINTER(C.c_uint64)]
         d.symaccel_batcher_submit_flac_restore.argtypes = [_vp, _vp, _vp, _vp, _vp, _u32, _sz, _sz, C.POINTER(C.c_uint64)]
         d.symaccel_batcher_submit_alac_predict.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, C.POINTER(C.c_uint64)]
+        d.symaccel_batcher_submit_adpcm_decode.argtypes = [_vp, _vp, _i, _sz, _sz, _sz, _vp, C.POINTER(C.c_uint64)]
         d.symaccel_aac_decode_pipelined.argtypes = [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _i, _vp, _i, _vp, _sz, _vp, _vp, _sz, _sz, _sz]
         d.symaccel_mp3_stereo_device.argtypes = [_vp, _vp, _sz, _vp, _vp, _i, _sz]
         d.symaccel_mp3_requantize_stereo_device.argtypes = [_vp, _vp, _vp, _sz, _vp, _vp, _i, _vp, _sz]
@@ -236,6 +242,10 @@ class Library:
         d.symaccel_sample_bytes.restype = _sz
         d.symaccel_pcm_convert_device.argtypes = [_vp, _vp, _i, _sz, _sz, _sz, _sz, _vp, _i, _sz]
         d.symaccel_pcm_convert.argtypes = [_vp, _vp, _i, _sz, _sz, _sz, _sz, _vp, _i, _sz]
+        d.symaccel_adpcm_block_bytes.argtypes = [_i, _sz, _sz]
+        d.symaccel_adpcm_block_bytes.restype = _sz
+        d.symaccel_adpcm_decode_device.argtypes = [_vp, _vp, _sz, _sz, _i, _sz, _sz, _vp, _i, _vp]
+        d.symaccel_adpcm_decode.argtypes = [_vp, _vp, _sz, _sz, _i, _sz, _sz, _vp, _i, _vp]
         d.symaccel_alac_block_status_device.argtypes = [_vp, _vp, _sz, _vp]
         d.symaccel_vorbis_floor1_status_device.argtypes = [_vp, _i, _vp, _sz, _vp]
         d.symaccel_aac_tns_status_device.argtypes = [_vp, _sz, _vp, _sz, _vp]

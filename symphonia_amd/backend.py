@@ -749,6 +749,47 @@ def pcm_convert_device(ctx, src, src_fmt, plane_stride, n_groups, channels, n_fr
               int(n_groups), int(channels), int(n_frames), (d + int(dst_offset)) if d is not None else None, sample_format(dst_fmt), int(dst_group_bytes))
 
 
+# ---- ADPCM: packet bytes to PCM (symaccel_adpcm_decode) --------------------------------------------------------------------------
+ADPCM_MS, ADPCM_IMA_WAV, ADPCM_IMA_QT = _ffi.ADPCM_MS, _ffi.ADPCM_IMA_WAV, _ffi.ADPCM_IMA_QT
+ADPCM_CODECS = {"ms": ADPCM_MS, "ima_wav": ADPCM_IMA_WAV, "ima_qt": ADPCM_IMA_QT}
+
+
+def adpcm_codec(codec):
+    """A SYMACCEL_ADPCM_* value from a value or a name ("ms", "ima_wav", "ima_qt")."""
+    return ADPCM_CODECS[codec.lower()] if isinstance(codec, str) else int(codec)
+
+
+def adpcm_block_bytes(codec, channels, frames_per_block, lib=None):
+    """symaccel_adpcm_block_bytes: bytes of one block; 0 for a shape the device decoder refuses (it belongs to the decoder below)."""
+    lib = lib if lib is not None else _ffi.default_library()
+    return int(lib.dll.symaccel_adpcm_block_bytes(adpcm_codec(codec), int(channels), int(frames_per_block)))
+
+
+def adpcm_decode(ctx, blocks, codec, channels, frames_per_block, out_fmt=0):
+    """symaccel_adpcm_decode: blocks[n_blocks, block_pitch] uint8 in host memory (a row holds one block, symphonia-codec-adpcm's
+    decode_mono / decode_stereo input) -> (pcm, status).  out_fmt 0: pcm int32[n_blocks, channels, frames_per_block], left-justified;
+    a format (value or name): uint8[n_blocks, frames_per_block * channels * sample_bytes], interleaved.  status uint8[n_blocks]: 0, 1 (MS
+    block predictor out of range: Unsupported), 2 (IMA WAV step index out of range: DecodeError); such a block is silence."""
+    b = np.ascontiguousarray(blocks, dtype=np.uint8)
+    if b.ndim != 2:
+        raise ValueError("blocks must be a [n_blocks, block_pitch] array of uint8")
+    codec, channels, fpb, out_fmt = adpcm_codec(codec), int(channels), int(frames_per_block), sample_format(out_fmt)
+    if out_fmt == 0:
+        pcm = np.zeros((b.shape[0], max(channels, 0), max(fpb, 0)), np.int32)
+    else:
+        pcm = np.zeros((b.shape[0], max(fpb * channels, 0) * sample_bytes(out_fmt, ctx.lib)), np.uint8)
+    status = np.zeros(b.shape[0], np.uint8)
+    ctx._call(ctx.lib.dll.symaccel_adpcm_decode, _ptr(b), b.shape[1], b.shape[0], codec, channels, fpb, _ptr(pcm), out_fmt, _ptr(status))
+    return pcm, status
+
+
+def adpcm_decode_device(ctx, src, block_pitch, n_blocks, codec, channels, frames_per_block, dst, out_fmt=0, status=None):
+    """symaccel_adpcm_decode_device on device memory (torch tensors, or raw addresses).  Asynchronous on the context's stream."""
+    ctx._call(ctx.lib.dll.symaccel_adpcm_decode_device, src if isinstance(src, int) else _ptr(src), int(block_pitch), int(n_blocks), adpcm_codec(codec),
+              int(channels), int(frames_per_block), dst if isinstance(dst, int) else _ptr(dst), sample_format(out_fmt),
+              status if isinstance(status, int) or status is None else _ptr(status))
+
+
 ALAC_DESC_DTYPE = np.dtype([("mode", np.uint8), ("lpc_order", np.uint8), ("shift", np.uint8), ("bps", np.uint8)])
 
 
@@ -903,6 +944,7 @@ class PinnedBuffer:
 
 BATCH_AAC_SYNTH, BATCH_MP3_SYNTH, BATCH_MP3_DECODE, BATCH_VORBIS_SYNTH, BATCH_AAC_DECODE = 1, 2, 3, 4, 5
 BATCH_VORBIS_DECODE, BATCH_FLAC_RESTORE, BATCH_ALAC_PREDICT = 6, 7, 8
+BATCH_ADPCM_DECODE = 9
 BATCH_MAX_INPUTS = 6
 
 
@@ -1056,6 +1098,18 @@ class Batcher:
         self._check(self.dll.symaccel_batcher_submit_alac_predict(
             self.handle, buf_io.ctypes.data, desc.ctypes.data, coeffs.ctypes.data, pair_weight.ctypes.data if pair_weight is not None else None,
             pair_shift.ctypes.data if pair_shift is not None else None, n_blocks, blocksize, C.byref(t)))
+        return int(t.value)
+
+    def submit_adpcm_decode(self, blocks, codec, channels, pcm, out_format=0):
+        """symaccel_batcher_submit_adpcm_decode: blocks uint8[n_blocks, block bytes] (the blocks of one packet, or of several), pcm
+        int32[n_blocks, channels, fpb] written by collect(); with out_format (a FMT_* value or name) `pcm` receives
+        [n_blocks][fpb][channels] samples of that format instead (symaccel_batcher_submit_fmt)"""
+        assert blocks.flags["C_CONTIGUOUS"] and pcm.flags["C_CONTIGUOUS"] and blocks.dtype == np.uint8 and blocks.ndim == 2
+        t = C.c_uint64()
+        if out_format:
+            return self.submit(BATCH_ADPCM_DECODE, adpcm_codec(codec) | int(channels) << 8, [blocks], [], pcm, out_format=out_format, channels=channels)
+        self._check(self.dll.symaccel_batcher_submit_adpcm_decode(self.handle, blocks.ctypes.data, adpcm_codec(codec), int(channels), int(blocks.shape[0]),
+                                                                  int(blocks.shape[1]), pcm.ctypes.data, C.byref(t)))
         return int(t.value)
 
     def reserve(self, kind, param, n_chains, units, out_format=0, channels=0):

@@ -250,3 +250,6 @@ int launch_batch_copy(symaccel_ctx *ctx, hipStream_t stream, const BatchCopyDesc
 }
 
 }  // namespace symaccel
+
+// The ADPCM decode kernels and their launcher (a file of their own, compiled as part of this translation unit)
+#include "adpcm.hip"

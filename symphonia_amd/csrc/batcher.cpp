@@ -167,6 +167,18 @@ bool plane_sizes(int kind, int param, size_t units, PlaneSizes *ps) {
         }
         ps->in_place = true;
         return true;
+    case SYMACCEL_BATCH_ADPCM_DECODE: {  // symaccel_adpcm_decode: bytes | no state | pcm; a chain is a BLOCK, units = its bytes
+        // param = codec | channels << 8 (| out_fmt << 16 inside the batcher: reserve_fmt folds the format into the group key, and the
+        // kernel itself writes the interleaved samples -- the scatter copies them as they are)
+        const int codec = param & 255, fmt = (param >> 16) & 255;
+        const size_t nch = (size_t)((param >> 8) & 255);
+        const size_t fpb = adpcm_frames_of_bytes(codec, nch, units);
+        if (param < 0 || (param >> 24) || fpb == 0 || (fmt != 0 && symaccel_sample_bytes(fmt) == 0)) return false;
+        ps->n_in = 1;
+        ps->in[0] = units;
+        ps->out = nch * fpb * (fmt ? symaccel_sample_bytes(fmt) : 4);
+        return true;
+    }
     default:
         return false;
     }
@@ -699,6 +711,11 @@ int launch_chunk(symaccel_ctx *ctx, Group *g, size_t c0, size_t nc, size_t t0, s
     case SYMACCEL_BATCH_ALAC_PREDICT:  // alac/lib.rs:165-264 (+ :664-671 with the pair parameters)
         return launch_alac_predict(ctx, (int32_t *)in(0), (const symaccel_alac_desc *)in(1), (const int32_t *)in(2), nc, g->units,
                                    (g->param & 0x100) ? (const int32_t *)in(3) : nullptr, (g->param & 0x100) ? (const uint8_t *)in(4) : nullptr, g->row_pitch / 4);
+    case SYMACCEL_BATCH_ADPCM_DECODE: {  // symphonia-codec-adpcm lib.rs:122-168 (the blocks of every packet in the chunk, side by side)
+        const int codec = g->param & 255, nch = (g->param >> 8) & 255;
+        return launch_adpcm_decode(ctx, ctx->stream, in(0), g->units, nc, codec, (unsigned)nch, (unsigned)adpcm_frames_of_bytes(codec, (size_t)nch, g->units), out,
+                                   (g->param >> 16) & 255, nullptr);
+    }
     default:
         return SYMACCEL_ERR_INVALID_ARG;
     }
@@ -775,6 +792,19 @@ int check_alac(const PlaneSizes &ps, int param, const TicketView &v) {
         for (size_t p = 0; p < v.n_chains / 2; ++p)
             if (sh[p] > 31) return SYMACCEL_ERR_INVALID_ARG;  // lib.rs:555
     }
+    return SYMACCEL_OK;
+}
+
+// An ADPCM_DECODE submission: the status its first rejected block has (symaccel_adpcm_decode_device's per-block status, read from the
+// preambles here: the reference stops a packet at its first bad block -- codec_ms.rs:25-29 Unsupported, codec_ima_wav.rs:17-19 DecodeError)
+int check_adpcm(size_t units, int param, const TicketView &v) {
+    const int codec = param & 255, nch = (param >> 8) & 255;
+    const uint8_t *b = reinterpret_cast<const uint8_t *>(v.slot);  // (in[0] is the slot's first plane)
+    for (size_t c = 0; c < v.n_chains; ++c, b += units)
+        for (int k = 0; k < nch; ++k) {
+            if (codec == SYMACCEL_ADPCM_MS && b[k] > 6) return SYMACCEL_ERR_UNSUPPORTED;
+            if (codec == SYMACCEL_ADPCM_IMA_WAV && b[4 * k + 2] > 88) return SYMACCEL_ERR_DECODE;
+        }
     return SYMACCEL_OK;
 }
 
@@ -894,6 +924,8 @@ int launch_group_inner(Lane *lane, Group *g, uint64_t *n_chunks, uint64_t *api_n
         for (TicketView &v : views) v.status = check_flac(ps, g->units, g->param, v);
     if (g->kind == SYMACCEL_BATCH_ALAC_PREDICT)
         for (TicketView &v : views) v.status = check_alac(ps, g->param, v);
+    if (g->kind == SYMACCEL_BATCH_ADPCM_DECODE)
+        for (TicketView &v : views) v.status = check_adpcm(g->units, g->param, v);
     if (g->kind == SYMACCEL_BATCH_VORBIS_DECODE) {
         for (TicketView &v : views) {
             size_t steps = 0;
@@ -1536,6 +1568,13 @@ int symaccel_batcher_reserve(symaccel_batcher *b, int kind, int param, size_t n_
 int symaccel_batcher_reserve_fmt(symaccel_batcher *b, int kind, int param, size_t n_chains, size_t units_per_chain, int out_fmt, int channels,
                                  symaccel_batch_slot *slot, uint64_t *ticket) {
     if (!b || !slot || !ticket || n_chains == 0 || units_per_chain == 0 || n_chains > 0x7fffffffu) return SYMACCEL_ERR_INVALID_ARG;
+    if (kind == SYMACCEL_BATCH_ADPCM_DECODE) {
+        // the interleave group is one block's channels, and the decode kernel itself writes the format: the format joins the group key,
+        // and from here on the submission is an ordinary one whose output plane holds [chain][frame][channel] samples of out_fmt
+        if (param < 0 || (param >> 16) || (out_fmt != 0 && (symaccel_sample_bytes(out_fmt) == 0 || channels != ((param >> 8) & 255)))) return SYMACCEL_ERR_INVALID_ARG;
+        param |= out_fmt << 16;
+        out_fmt = channels = 0;
+    }
     if (out_fmt != 0 && (symaccel_sample_bytes(out_fmt) == 0 || channels < 1 || channels > 8 || n_chains % (size_t)channels != 0)) return SYMACCEL_ERR_INVALID_ARG;
     PlaneSizes ps;
     if (kind == SYMACCEL_BATCH_AAC_SYNTH) param = 0;
@@ -1743,6 +1782,7 @@ int symaccel_batcher_submit_fmt(symaccel_batcher *b, int kind, int param, size_t
     if (!b || !in || !state_io || !out || !ticket) return SYMACCEL_ERR_INVALID_ARG;
     if (kind == SYMACCEL_BATCH_AAC_DECODE) return SYMACCEL_ERR_INVALID_ARG;  // (symaccel_batcher_submit_aac_decode writes the blob)
     PlaneSizes ps;
+    if (kind == SYMACCEL_BATCH_ADPCM_DECODE && (param < 0 || (param >> 16))) return SYMACCEL_ERR_INVALID_ARG;  // (the format travels in out_fmt)
     if (!plane_sizes(kind, kind == SYMACCEL_BATCH_AAC_SYNTH ? 0 : param, units_per_chain, &ps)) return SYMACCEL_ERR_INVALID_ARG;
     for (int i = 0; i < ps.n_in; ++i)
         if (!in[i] && !(kind == SYMACCEL_BATCH_MP3_DECODE && i == 3 && n_chains == 1)) return SYMACCEL_ERR_INVALID_ARG;
@@ -1926,6 +1966,14 @@ int symaccel_batcher_submit_flac_restore(symaccel_batcher *b, int32_t *buf_io, c
     const void *in[kMaxIn] = {buf_io, desc, coeffs, pair_mode, nullptr, nullptr};
     void *st[3] = {nullptr, nullptr, nullptr};
     return symaccel_batcher_submit(b, SYMACCEL_BATCH_FLAC_RESTORE, pair_mode ? (int)(0x100 | out_shift) : 0, n_blocks, blocksize, in, st, buf_io, ticket);
+}
+
+int symaccel_batcher_submit_adpcm_decode(symaccel_batcher *b, const uint8_t *bytes, int codec, size_t channels, size_t n_blocks, size_t block_bytes,
+                                        int32_t *pcm, uint64_t *ticket) {
+    if (codec < 0 || codec > 255 || channels > 255) return SYMACCEL_ERR_INVALID_ARG;
+    const void *in[kMaxIn] = {bytes, nullptr, nullptr, nullptr, nullptr, nullptr};
+    void *st[3] = {nullptr, nullptr, nullptr};
+    return symaccel_batcher_submit(b, SYMACCEL_BATCH_ADPCM_DECODE, codec | (int)(channels << 8), n_blocks, block_bytes, in, st, pcm, ticket);
 }
 
 int symaccel_batcher_submit_alac_predict(symaccel_batcher *b, int32_t *buf_io, const symaccel_alac_desc *desc, const int32_t *coeffs,

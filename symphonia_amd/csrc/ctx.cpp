@@ -1181,6 +1181,28 @@ int symaccel_pcm_convert_device(symaccel_ctx *ctx, const void *d_src, int src_fm
     return launch_pcm_convert(ctx, ctx->stream, d_src, src_fmt, plane_stride, n_groups, channels, n_frames, d_dst, dst_fmt, dst_group_bytes);
 }
 
+// ---- ADPCM ------------------------------------------------------------------------------------
+
+size_t symaccel_adpcm_block_bytes(int codec, size_t channels, size_t frames_per_block) { return adpcm_block_bytes(codec, channels, frames_per_block); }
+
+int symaccel_adpcm_decode_device(symaccel_ctx *ctx, const void *d_bytes, size_t block_pitch, size_t n_blocks, int codec, size_t channels,
+                                 size_t frames_per_block, void *d_pcm, int out_fmt, uint8_t *d_status) {
+    if (!ctx) return SYMACCEL_ERR_INVALID_ARG;
+    SYM_TRY(adpcm_shape_status(block_pitch, n_blocks, codec, channels, frames_per_block, out_fmt));
+    if (n_blocks == 0) return SYMACCEL_OK;
+    if (!d_bytes || !d_pcm) return SYMACCEL_ERR_INVALID_ARG;
+    const size_t b = out_fmt == 0 ? 4 : symaccel_sample_bytes(out_fmt);
+    const uintptr_t s0 = (uintptr_t)d_bytes, t0 = (uintptr_t)d_pcm, u0 = (uintptr_t)d_status;
+    if ((b == 2 || b == 4) && t0 % b != 0) return SYMACCEL_ERR_INVALID_ARG;
+    const size_t src_bytes = (n_blocks - 1) * block_pitch + adpcm_block_bytes(codec, channels, frames_per_block);
+    const size_t dst_bytes = n_blocks * channels * frames_per_block * b;
+    if (s0 < t0 + dst_bytes && t0 < s0 + src_bytes) return SYMACCEL_ERR_INVALID_ARG;  // overlapping buffers
+    if (d_status && ((u0 < t0 + dst_bytes && t0 < u0 + n_blocks) || (u0 < s0 + src_bytes && s0 < u0 + n_blocks))) return SYMACCEL_ERR_INVALID_ARG;
+    DeviceGuard dev(ctx);
+    if (!dev.ok()) return dev.status();
+    return launch_adpcm_decode(ctx, ctx->stream, d_bytes, block_pitch, n_blocks, codec, (unsigned)channels, (unsigned)frames_per_block, d_pcm, out_fmt, d_status);
+}
+
 // ---- per-record status arrays --------------------------------------------------------------
 
 int symaccel_flac_block_status_device(symaccel_ctx *ctx, const symaccel_flac_desc *d_desc, size_t n_blocks, size_t blocksize,

@@ -484,6 +484,51 @@ int symaccel_pcm_convert(symaccel_ctx *ctx, const void *h_src, int src_fmt, size
     return pp.drain();
 }
 
+// symaccel_adpcm_decode_device between host buffers: chunks of whole blocks.  On the device a chunk's blocks sit at a pitch that is a
+// multiple of 16 bytes, so that every 16-byte unit of a block's image belongs to that block alone.
+int symaccel_adpcm_decode(symaccel_ctx *ctx, const void *h_bytes, size_t block_pitch, size_t n_blocks, int codec, size_t channels,
+                          size_t frames_per_block, void *h_pcm, int out_fmt, uint8_t *h_status) {
+    if (!ctx) return SYMACCEL_ERR_INVALID_ARG;
+    SYM_TRY(adpcm_shape_status(block_pitch, n_blocks, codec, channels, frames_per_block, out_fmt));
+    if (n_blocks == 0) return SYMACCEL_OK;
+    if (!h_bytes || !h_pcm) return SYMACCEL_ERR_INVALID_ARG;
+    const size_t bytes = adpcm_block_bytes(codec, channels, frames_per_block), d_pitch = (bytes + 15) & ~(size_t)15;
+    const size_t out_bytes = channels * frames_per_block * (out_fmt == 0 ? 4 : symaccel_sample_bytes(out_fmt));
+    const uintptr_t s0 = (uintptr_t)h_bytes, t0 = (uintptr_t)h_pcm;
+    if (s0 < t0 + n_blocks * out_bytes && t0 < s0 + (n_blocks - 1) * block_pitch + bytes) return SYMACCEL_ERR_INVALID_ARG;  // overlapping buffers
+    DeviceGuard dev(ctx);
+    if (!dev.ok()) return dev.status();
+    const size_t cb = pick_chunk(n_blocks, d_pitch + out_bytes, 0);
+    Pipe pp(ctx);
+    SYM_TRY(pp.init());
+    uint8_t *d_in[2], *d_out[2], *d_st[2];
+    for (int k = 0; k < 2; ++k) {
+        SYM_TRY(pp.alloc((void **)&d_in[k], cb * d_pitch));
+        SYM_TRY(pp.alloc((void **)&d_out[k], cb * out_bytes));
+        SYM_TRY(pp.alloc((void **)&d_st[k], cb));
+    }
+    SYM_TRY(pp.commit());
+    size_t k = 0;
+    for (size_t b0 = 0; b0 < n_blocks; b0 += cb, ++k) {
+        const size_t nb = std::min(cb, n_blocks - b0);
+        const int bi = (int)(k & 1);
+        if (k >= 2) {  // buffer set bi is free once chunk k-2's kernel has read its input and its output has left
+            SYM_GPU(ctx, hipStreamWaitEvent(pp.s_in, pp.ev_k[bi], 0));
+            SYM_GPU(ctx, hipStreamWaitEvent(ctx->stream, pp.ev_out[bi], 0));
+        }
+        SYM_TRY(copy_rows(ctx, d_in[bi], d_pitch, static_cast<const uint8_t *>(h_bytes) + b0 * block_pitch, block_pitch, bytes, nb, hipMemcpyHostToDevice, pp.s_in));
+        SYM_GPU(ctx, hipEventRecord(pp.ev_in[bi], pp.s_in));
+        SYM_GPU(ctx, hipStreamWaitEvent(ctx->stream, pp.ev_in[bi], 0));
+        SYM_TRY(launch_adpcm_decode(ctx, ctx->stream, d_in[bi], d_pitch, nb, codec, (unsigned)channels, (unsigned)frames_per_block, d_out[bi], out_fmt, d_st[bi]));
+        SYM_GPU(ctx, hipEventRecord(pp.ev_k[bi], ctx->stream));
+        SYM_GPU(ctx, hipStreamWaitEvent(pp.s_out, pp.ev_k[bi], 0));
+        SYM_GPU(ctx, hipMemcpyAsync(static_cast<uint8_t *>(h_pcm) + b0 * out_bytes, d_out[bi], nb * out_bytes, hipMemcpyDeviceToHost, pp.s_out));
+        if (h_status) SYM_GPU(ctx, hipMemcpyAsync(h_status + b0, d_st[bi], nb, hipMemcpyDeviceToHost, pp.s_out));
+        SYM_GPU(ctx, hipEventRecord(pp.ev_out[bi], pp.s_out));
+    }
+    return pp.drain();
+}
+
 int symaccel_flac_restore_pipelined(symaccel_ctx *ctx, int32_t *h_buf, const symaccel_flac_desc *h_desc, const int32_t *h_coeffs,
                                     size_t n_blocks, size_t blocksize, size_t chunk_blocks) {
     if (!ctx || blocksize > 65535) return SYMACCEL_ERR_INVALID_ARG;

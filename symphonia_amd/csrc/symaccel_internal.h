@@ -317,6 +317,46 @@ inline bool pcm_convert_shape_ok(int src_fmt, size_t plane_stride, size_t n_grou
     if (plane_stride < n_frames || dst_group_bytes < n_frames * channels * b) return false;
     return !((b == 2 || b == 4) && dst_group_bytes % b != 0);
 }
+// adpcm.hip: bytes of one block (symphonia-codec-adpcm: codec_ms.rs:101-136, codec_ima_wav.rs:27-65, codec_ima_qt.rs:24-47), 0 for the
+// shapes the device decoder refuses: those where the reference leaves samples of a block unwritten or indexes out of range (MS with
+// fewer than 2 frames or a mono block of odd length, IMA WAV mono of even length, IMA WAV stereo unless (fpb - 1) % 8 == 0, IMA QT other
+// than 64 frames), more than two channels (lib.rs:97-99), and more than kAdpcmMaxFrames frames (keeps a block's offsets in 32 bits)
+constexpr size_t kAdpcmMaxFrames = (size_t)1 << 20;
+inline size_t adpcm_block_bytes(int codec, size_t channels, size_t fpb) {
+    if ((channels != 1 && channels != 2) || fpb == 0 || fpb > kAdpcmMaxFrames) return 0;
+    switch (codec) {
+    case SYMACCEL_ADPCM_MS:
+        if (fpb < 2 || (channels == 1 && fpb % 2 != 0)) return 0;
+        return channels == 1 ? 6 + fpb / 2 : 12 + fpb;
+    case SYMACCEL_ADPCM_IMA_WAV:
+        if (channels == 1) return fpb % 2 == 0 ? 0 : 4 + (fpb - 1) / 2;
+        return (fpb - 1) % 8 != 0 ? 0 : 7 + fpb;
+    case SYMACCEL_ADPCM_IMA_QT: return fpb != 64 ? 0 : 34 * channels;
+    default: return 0;
+    }
+}
+// the frames of a block of `bytes` bytes (the inverse of the table above), 0 if no accepted shape has that many
+inline size_t adpcm_frames_of_bytes(int codec, size_t channels, size_t bytes) {
+    size_t fpb = 0;
+    switch (codec) {
+    case SYMACCEL_ADPCM_MS: fpb = channels == 1 ? (bytes >= 7 ? 2 * (bytes - 6) : 0) : (bytes >= 14 ? bytes - 12 : 0); break;
+    case SYMACCEL_ADPCM_IMA_WAV: fpb = channels == 1 ? (bytes >= 4 ? 2 * (bytes - 4) + 1 : 0) : (bytes >= 8 ? bytes - 7 : 0); break;
+    case SYMACCEL_ADPCM_IMA_QT: fpb = 64; break;
+    default: break;
+    }
+    return fpb != 0 && adpcm_block_bytes(codec, channels, fpb) == bytes ? fpb : 0;
+}
+// what symaccel_adpcm_decode(_device) refuse, pointers aside: SYMACCEL_OK, or the error
+inline int adpcm_shape_status(size_t block_pitch, size_t n_blocks, int codec, size_t channels, size_t fpb, int out_fmt) {
+    if (codec != SYMACCEL_ADPCM_MS && codec != SYMACCEL_ADPCM_IMA_WAV && codec != SYMACCEL_ADPCM_IMA_QT) return SYMACCEL_ERR_INVALID_ARG;
+    if (out_fmt != 0 && symaccel_sample_bytes(out_fmt) == 0) return SYMACCEL_ERR_INVALID_ARG;
+    if (n_blocks > (size_t)1 << 32 || block_pitch > (size_t)1 << 24) return SYMACCEL_ERR_INVALID_ARG;
+    const size_t bytes = adpcm_block_bytes(codec, channels, fpb);
+    if (bytes == 0) return SYMACCEL_ERR_UNSUPPORTED;
+    return block_pitch < bytes ? SYMACCEL_ERR_INVALID_ARG : SYMACCEL_OK;
+}
+int launch_adpcm_decode(symaccel_ctx *ctx, hipStream_t stream, const void *d_bytes, size_t block_pitch, size_t n_blocks, int codec, unsigned channels,
+                        unsigned frames_per_block, void *d_pcm, int out_fmt, uint8_t *d_status);
 int launch_probe_copy(symaccel_ctx *ctx, const void *d_src, void *d_dst, size_t bytes, unsigned frames_per_wavefront, unsigned flags);
 int launch_flac_decorrelate(symaccel_ctx *ctx, const uint8_t *d_mode, int32_t *d_ch0, int32_t *d_ch1,
                             size_t n_pairs, size_t blocksize, uint32_t out_shift);

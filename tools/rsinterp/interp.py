@@ -3246,6 +3246,10 @@ class Interp:
                 return good
             if name in ('is_none', 'is_err'):
                 return not good
+            if name == 'is_none_or' and v.enum == 'Option':  # std: true for None, else the predicate of the value
+                return truth(self.call_value(args[0], [v.f['0']])) if good else True
+            if name == 'is_some_and' and v.enum == 'Option':
+                return truth(self.call_value(args[0], [v.f['0']])) if good else False
             if name == 'unwrap_or':
                 return v.f['0'] if good else args[0]
             if name == 'unwrap_or_default':
