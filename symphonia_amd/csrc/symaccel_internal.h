@@ -295,6 +295,9 @@ struct BatchCopyDesc {
 };
 constexpr size_t kBatchCopyPiece = 16384;
 constexpr uint32_t kBatchPieceConvert = 0x80000000u, kBatchPieceFromI32 = 0x10u;
+constexpr uint32_t batch_piece_convert(bool from_i32, size_t frames, uint32_t channels, int dst_fmt) {  // the `pad` word of a converting piece
+    return kBatchPieceConvert | (from_i32 ? kBatchPieceFromI32 : 0u) | ((uint32_t)frames << 12) | (channels << 8) | (uint32_t)dst_fmt;
+}
 int launch_batch_copy(symaccel_ctx *ctx, hipStream_t stream, const BatchCopyDesc *descs, size_t n, bool scatter, size_t pcm_plane_stride = 0);
 int launch_batch_flag(symaccel_ctx *ctx, hipStream_t stream, uint64_t *h_flag, uint64_t seq);  // (h_flag: page-locked host memory)
 // pcm_convert.h works in tiles: a frame range of one interleave group whose output is contiguous and at most kPcmTileBytes long (the piece

@@ -109,7 +109,9 @@ def run_mp3_synth(ctx):
     for (xr, side, ov, vv, vf, want), pcm in zip(streams, pcms):
         assert bit_equal(pcm, np.asarray(want[0])) and bit_equal(ov, np.asarray(want[1])) and bit_equal(vv, np.asarray(want[2]))
         assert np.array_equal(vf, np.asarray(want[3]))
+    st = b.stats()
     b.close()
+    return st
 
 
 def test_emu_mp3_synth_streams(emu_ctx):
@@ -140,8 +142,10 @@ def run_mp3_decode(ctx, n_streams=5, granules=6):
         b.collect(t)
         assert bit_equal(pcm, np.asarray(want[0])), "pcm"
         assert bit_equal(ov, np.asarray(want[1])) and bit_equal(vv, np.asarray(want[2])) and np.array_equal(vf, np.asarray(want[3]))
-    assert b.stats()["launches"] == 1 and b.stats()["submissions"] == n_streams
+    st = b.stats()
+    assert st["launches"] == 1 and st["submissions"] == n_streams
     b.close()
+    return st
 
 
 def test_emu_mp3_decode_streams(emu_ctx):
@@ -182,7 +186,9 @@ def run_vorbis(ctx, bs0e, bs1e, n_streams=5, nb=11):
         b.reserve(BATCH_VORBIS_SYNTH, 5 | (11 << 8), 1, 4)   # 32-sample blocks do not exist
     with pytest.raises(Exception):
         b.reserve(BATCH_VORBIS_SYNTH, 11 | (8 << 8), 1, 4)   # bs0 > bs1
+    st = b.stats()
     b.close()
+    return st
 
 
 @pytest.mark.parametrize("bs0e,bs1e", [(8, 11), (6, 9)])
@@ -223,8 +229,10 @@ def run_aac_decode(ctx, n_streams=5, frames=7, seed0=900):
         b.submit_aac_decode(bands, coeffs, side, np.array([[0, 2]], np.int32), desc, None, delay.copy(), pcm)
     with pytest.raises(Exception):
         b.submit_aac_decode(bands + 7, coeffs, side, None, None, None, delay.copy(), pcm)
-    assert b.stats()["pending"] == 0
+    st = b.stats()
+    assert st["pending"] == 0
     b.close()
+    return st
 
 
 def test_emu_aac_decode_streams_share_a_launch(emu_ctx):

@@ -61,6 +61,7 @@ def check_sharing(ctx):
     for t, blocks, codec, ch, fpb, out in subs[:6]:  # the per-stream entry point gives the same
         pcm, status = adpcm_decode(ctx, blocks, codec, ch, fpb)
         assert np.array_equal(pcm, out) and not status.any()
+    return st
 
 
 def check_bad_block(ctx):
@@ -124,7 +125,9 @@ def check_formats(ctx):
         with pytest.raises(SymaccelError) as e:
             b.reserve(BATCH_ADPCM_DECODE, bad[0], bad[1], bad[2], out_format=bad[3], channels=bad[4])
         assert e.value.status == _ffi.ERR_INVALID_ARG
+    st = b.stats()
     b.close()
+    return st
 
 
 def check_reserve_refusals(ctx):

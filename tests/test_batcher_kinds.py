@@ -68,6 +68,7 @@ def run_vorbis_decode(ctx, bs0e, bs1e, shapes=((2, 3), (1, 2), (3, 1)), nb=7):
     st = b.stats()
     assert st["launches"] == len(shapes) and st["failed_tickets"] == 0, st
     b.close()
+    return st
 
 
 @pytest.mark.parametrize("bs0e,bs1e", [(8, 11), (6, 9), (8, 8)])
@@ -101,6 +102,7 @@ def run_vorbis_decode_bad_ticket(ctx):
     st = b.stats()
     assert st["launches"] == 1 and st["failed_tickets"] == 3 and st["pending"] == 0, st
     b.close()
+    return st
 
 
 def test_emu_vorbis_decode_bad_submission_fails_alone(emu_ctx):
@@ -165,7 +167,9 @@ def run_flac(ctx, blocksize=100):
         b.reserve(BATCH_FLAC_RESTORE, 0x108, 3, 64)  # pairs: an even number of subframes
     with pytest.raises(Exception):
         b.reserve(BATCH_FLAC_RESTORE, 0, 2, 65536)   # frame.rs:58: a block size has 16 bits
+    st = b.stats()
     b.close()
+    return st
 
 
 def test_emu_flac_streams_share_a_launch(emu_ctx):
@@ -223,7 +227,9 @@ def run_alac(ctx, blocksize=100):
     assert e.value.status == -5
     b.collect(ok)
     assert np.array_equal(got2, oracle.alac_predict(buf2, oracle.alac_desc(mode2, order2, shift2, bps2), coeffs2))
+    st = b.stats()
     b.close()
+    return st
 
 
 def test_emu_alac_streams_share_a_launch(emu_ctx):
@@ -266,6 +272,7 @@ def run_bad_aac_blob(ctx):
     st = b.stats()
     assert st["failed_tickets"] == 1 and st["pending"] == 0, st
     b.close()
+    return st
 
 
 def test_emu_bad_blob_fails_alone(emu_ctx):

@@ -230,6 +230,7 @@ def check_kind(ctx, name):
         assert len(r1["out"]) == len(want), (name, i, fmt, len(r1["out"]), len(want))
         bad = np.flatnonzero((r1["out"] != want) & defined)
         assert bad.size == 0, "%s ticket %d (%s x %d): %d bytes differ, first at %d" % (name, i, fmt, ch, bad.size, bad[0])
+    return st0, st1
 
 
 @pytest.mark.parametrize("name", list(KINDS))
