@@ -531,17 +531,13 @@ int symaccel_mp3_synth_device(symaccel_ctx *ctx, const float *d_xr, const symacc
     if (!d_xr || !d_side || !d_overlap_io || !d_vvec_io || !d_vfront_io || !d_pcm) return SYMACCEL_ERR_INVALID_ARG;
     DeviceGuard dev(ctx);
     if (!dev.ok()) return dev.status();
-    const size_t ov_bytes = n_chains * 576 * 4, vv_bytes = n_chains * 1024 * 4, vf_bytes = n_chains * 4;
     void *scratch = nullptr;
-    SYM_TRY(ctx_scratch(ctx, ov_bytes + vv_bytes + vf_bytes, &scratch));
-    float *ov_out = (float *)scratch;
-    float *vv_out = ov_out + n_chains * 576;
-    int32_t *vf_out = (int32_t *)(vv_out + n_chains * 1024);
-    SYM_TRY(launch_mp3(ctx, d_xr, d_side, sample_rate_idx, d_overlap_io, d_vvec_io, d_vfront_io, ov_out, vv_out,
-                       vf_out, d_pcm, n_chains, granules_per_chain));
-    SYM_TRY(launch_state_copy(ctx, d_overlap_io, ov_out, ov_bytes, d_vvec_io, vv_out, vv_bytes, d_vfront_io, vf_out,
-                              vf_bytes));
-    return SYMACCEL_OK;
+    SYM_TRY(ctx_scratch(ctx, Mp3State::bytes(n_chains), &scratch));
+    const Mp3State out = Mp3State::carve(scratch, n_chains);
+    SYM_TRY(launch_mp3(ctx, d_xr, d_side, sample_rate_idx, d_overlap_io, d_vvec_io, d_vfront_io, out.overlap, out.vvec, out.vfront, d_pcm,
+                       n_chains, granules_per_chain));
+    return launch_state_copy(ctx, d_overlap_io, out.overlap, n_chains * Mp3State::kOverlap, d_vvec_io, out.vvec, n_chains * Mp3State::kVvec,
+                             d_vfront_io, out.vfront, n_chains * Mp3State::kVfront);
 }
 
 int symaccel_mp3_decode_pp_device(symaccel_ctx *ctx, const int16_t *d_quant, const symaccel_mp3_requant *d_rq_desc,
@@ -571,16 +567,13 @@ int symaccel_mp3_decode_device(symaccel_ctx *ctx, const int16_t *d_quant, const 
     if (!d_overlap_io || !d_vvec_io || !d_vfront_io) return SYMACCEL_ERR_INVALID_ARG;
     DeviceGuard dev(ctx);
     if (!dev.ok()) return dev.status();
-    const size_t ov_bytes = n_chains * 576 * 4, vv_bytes = n_chains * 1024 * 4, vf_bytes = n_chains * 4;
     void *scratch = nullptr;
-    SYM_TRY(ctx_scratch(ctx, ov_bytes + vv_bytes + vf_bytes, &scratch));
-    float *ov_out = (float *)scratch;
-    float *vv_out = ov_out + n_chains * 576;
-    int32_t *vf_out = (int32_t *)(vv_out + n_chains * 1024);
+    SYM_TRY(ctx_scratch(ctx, Mp3State::bytes(n_chains), &scratch));
+    const Mp3State out = Mp3State::carve(scratch, n_chains);
     SYM_TRY(symaccel_mp3_decode_pp_device(ctx, d_quant, d_rq_desc, d_unit_chains, d_st_desc, n_units, d_side, sample_rate_idx, d_overlap_io,
-                                          d_vvec_io, d_vfront_io, ov_out, vv_out, vf_out, d_pcm, n_chains, granules_per_chain));
-    SYM_TRY(launch_state_copy(ctx, d_overlap_io, ov_out, ov_bytes, d_vvec_io, vv_out, vv_bytes, d_vfront_io, vf_out, vf_bytes));
-    return SYMACCEL_OK;
+                                          d_vvec_io, d_vfront_io, out.overlap, out.vvec, out.vfront, d_pcm, n_chains, granules_per_chain));
+    return launch_state_copy(ctx, d_overlap_io, out.overlap, n_chains * Mp3State::kOverlap, d_vvec_io, out.vvec, n_chains * Mp3State::kVvec,
+                             d_vfront_io, out.vfront, n_chains * Mp3State::kVfront);
 }
 
 int symaccel_mp3_synth(symaccel_ctx *ctx, const float *h_xr, const symaccel_mp3_side *h_side, int sample_rate_idx,

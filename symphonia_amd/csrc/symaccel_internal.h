@@ -205,6 +205,18 @@ inline size_t aac_js_scratch_bytes(size_t n_chains, size_t n_pairs, size_t frame
     (void)frames_per_chain;
     return ((n_chains * 8 + 255) & ~(size_t)255) + 256;
 }
+// The state an MP3 chain carries from call to call, as three planes back to back in one device block (k*: bytes per chain)
+struct Mp3State {
+    float *overlap;   // [n_chains][576]
+    float *vvec;      // [n_chains][1024]
+    int32_t *vfront;  // [n_chains]
+    static constexpr size_t kOverlap = 576 * 4, kVvec = 1024 * 4, kVfront = 4;
+    static size_t bytes(size_t n_chains) { return n_chains * (kOverlap + kVvec + kVfront); }
+    static Mp3State carve(void *base, size_t n_chains) {
+        char *p = static_cast<char *>(base);
+        return {(float *)p, (float *)(p + n_chains * kOverlap), (int32_t *)(p + n_chains * (kOverlap + kVvec))};
+    }
+};
 int launch_mp3(symaccel_ctx *ctx, const float *d_xr, const symaccel_mp3_side *d_side, int sr,
                const float *d_overlap_in, const float *d_vvec_in, const int32_t *d_vfront_in,
                float *d_overlap_out, float *d_vvec_out, int32_t *d_vfront_out, float *d_pcm,

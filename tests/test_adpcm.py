@@ -215,6 +215,26 @@ def check_host_equals_resident(dev):
     assert pcm.shape == (0, 1, 64) and status.shape == (0,)
 
 
+def check_host_in_two_chunks(dev):
+    """symaccel_adpcm_decode cuts its batch where a chunk's blocks and their output reach 32 MiB.  MS stereo at 1012 frames per block
+    is 1024 bytes in and 8096 out (native i32), so a chunk holds floor(32 MiB / (1024 + 8096)) = 3679 blocks; 3679 + 5 blocks are a full
+    chunk and a tail of 5, whose blocks, PCM and status bytes sit at the second chunk's offsets into the caller's arrays.  Every third
+    block is bad, so the status bytes differ on both sides of the cut.  Expected: the resident result on the same bytes, and the
+    restatement for blocks on both sides of the cut."""
+    codec, ch, fpb, cut = "ms", 2, 1012, 3679
+    assert R.block_bytes(CODEC[codec], ch, fpb) == 1024 and (32 << 20) // (1024 + ch * fpb * 4) == cut
+    n = cut + 5
+    b = arbitrary(np.random.default_rng(41), codec, ch, fpb, n, bad_every=3)
+    padded = np.concatenate([b, np.full((n, 5), 0x77, np.uint8)], axis=1)  # a host pitch above the block's bytes
+    res, res_status = run_device(dev, b, codec, ch, fpb)
+    pcm, status = adpcm_decode(dev.ctx, padded, codec, ch, fpb)
+    assert np.array_equal(status, res_status) and np.array_equal(pcm.view(np.uint8).reshape(n, -1), res)
+    pick = np.r_[0:3, cut - 4:n]
+    want, want_status = R.decode(b[pick], codec, ch, fpb)
+    assert want_status[pick < cut].any() and want_status[pick >= cut].any() and not want_status[pick >= cut].all()
+    assert np.array_equal(status[pick], want_status) and np.array_equal(pcm[pick], want)
+
+
 def test_kernel_equals_the_reference_fixture(emu_dev):
     check_fixture(emu_dev)
 
@@ -239,6 +259,10 @@ def test_more_tiles_than_the_grid(emu_dev):
 
 def test_host_to_host_equals_resident(emu_dev):
     check_host_equals_resident(emu_dev)
+
+
+def test_host_to_host_in_two_chunks_equals_resident(emu_dev):
+    check_host_in_two_chunks(emu_dev)
 
 
 def test_refused_shapes_and_bad_arguments(emu_ctx):  # noqa: F811
@@ -304,6 +328,11 @@ def test_gpu_more_tiles_than_the_grid(gpu_dev):
 @pytest.mark.gpu
 def test_gpu_host_to_host_equals_resident(gpu_dev):
     check_host_equals_resident(gpu_dev)
+
+
+@pytest.mark.gpu
+def test_gpu_host_to_host_in_two_chunks_equals_resident(gpu_dev):
+    check_host_in_two_chunks(gpu_dev)
 
 
 @pytest.mark.gpu

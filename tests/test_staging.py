@@ -43,16 +43,19 @@ def run_mp3(ctx, chunks):
             assert bit_equal(a, np.asarray(b)), ch
 
 
-def run_flac(ctx, chunks):
+def flac_case(nb, bs):
     rng = np.random.default_rng(3)
-    nb, bs = 37, 96
     buf = rng.integers(-2000, 2000, (nb, bs)).astype(np.int32)
     kind, order = rng.integers(0, 3, nb), rng.integers(1, 5, nb)
     order[kind == 2] = rng.integers(1, 33, int((kind == 2).sum()))
     shift = rng.integers(0, 15, nb)
     co = (rng.integers(-300, 300, (nb, 32)) * 0.6 ** np.arange(32)).astype(np.int32)
     desc = flac_desc(kind, order, shift, np.zeros(nb))
-    want = oracle.flac_restore(buf, oracle.flac_desc(kind, order, shift, 0 * shift), co)
+    return buf, desc, co, oracle.flac_restore(buf, oracle.flac_desc(kind, order, shift, 0 * shift), co)
+
+
+def run_flac(ctx, chunks):
+    buf, desc, co, want = flac_case(37, 96)
     for ch in chunks:
         assert np.array_equal(FlacPredictor(ctx).restore(buf, desc, co, chunk_blocks=ch), want), ch
 
@@ -102,3 +105,21 @@ def test_gpu_staged_aac_on_pinned_memory_matches_the_one_shot_path(gpu_ctx):
     assert bit_equal(pp.array[pick], want)
     pc.free()
     pp.free()
+
+
+@pytest.mark.gpu
+def test_gpu_staged_flac_in_place_on_pinned_memory_equals_the_oracle(gpu_ctx):
+    """FLAC restores in place, so its chunks follow run_chunks' in-place order (csrc/stage.cpp): a buffer is refilled once its
+    result has left.  64 blocks of 4096 samples in chunks of 8 -- eight chunks, each buffer set reused three times -- with the
+    samples, descriptors and coefficients in page-locked memory, the only kind on which the three streams run concurrently.
+    A run this small cannot prove the absence of a race: what it pins is that the in-place order runs on page-locked memory at
+    all and gives the oracle's samples; the order itself is reviewed against the rules at the head of run_chunks."""
+    from symphonia_amd import PinnedBuffer
+    buf, desc, co, want = flac_case(64, 4096)
+    pinned = [PinnedBuffer(a.shape, a.dtype) for a in (buf, desc, co)]
+    for p, a in zip(pinned, (buf, desc, co)):
+        p.array[...] = a
+    gpu_ctx._call(gpu_ctx.lib.dll.symaccel_flac_restore_pipelined, *(p.array.ctypes.data for p in pinned), 64, 4096, 8)
+    assert np.array_equal(pinned[0].array, want)
+    for p in pinned:
+        p.free()
