@@ -34,6 +34,7 @@ mod flac;
 pub mod frontends;
 mod lookahead;
 mod mpa;
+pub mod mpa12;
 mod pcm;
 mod vorbis;
 
@@ -45,6 +46,7 @@ pub use ctx::{Context, Pinned, Pool};
 pub use flac::{FlacFrontEnd, HipFlacDecoder, ParsedFlac};
 pub use lookahead::{find_reader, BatchCodec, Lookahead, LookaheadReader, PacketKey, Shared, SharedHandle, TrackQueue};
 pub use mpa::{HipMpaDecoder, MpaFrontEnd, ParsedMpa};
+pub use mpa12::{HipMpa12Decoder, MpaLayer};
 pub use pcm::{SampleFormat, SourceSample};
 pub use vorbis::{HipVorbisDecoder, ParsedVorbis, VorbisFrontEnd};
 

@@ -52,7 +52,7 @@
 extern "C" {
 #endif
 
-#define SYMACCEL_ABI_VERSION 8 /* 2: *_pp_device entry points, per-block status arrays, lookahead staging; 3: multi-GPU, probe; 4: mp3_decode_*device, vorbis floor_y; 5: aac_decode_pipelined, aac_joint_stereo_list, vorbis_decode; 6: batcher; 7: batch kinds for Vorbis from posts, FLAC and ALAC (symaccel_batch_slot has six input planes), lanes, per-ticket status; 8: *_strided_device (padded row pitch for the FLAC / ALAC planes), symaccel_row_stride; additions within 8: symaccel_md5_*, symaccel_flac_md5(_device) (STREAMINFO MD5), SYMACCEL_FMT_*, symaccel_sample_bytes, symaccel_pcm_convert(_device), symaccel_batcher_reserve_fmt / _submit_fmt */
+#define SYMACCEL_ABI_VERSION 8 /* 2: *_pp_device entry points, per-block status arrays, lookahead staging; 3: multi-GPU, probe; 4: mp3_decode_*device, vorbis floor_y; 5: aac_decode_pipelined, aac_joint_stereo_list, vorbis_decode; 6: batcher; 7: batch kinds for Vorbis from posts, FLAC and ALAC (symaccel_batch_slot has six input planes), lanes, per-ticket status; 8: *_strided_device (padded row pitch for the FLAC / ALAC planes), symaccel_row_stride; additions within 8: symaccel_md5_*, symaccel_flac_md5(_device) (STREAMINFO MD5), SYMACCEL_FMT_*, symaccel_sample_bytes, symaccel_pcm_convert(_device), symaccel_batcher_reserve_fmt / _submit_fmt, symaccel_adpcm_*, symaccel_mpa12_* (Layer I / II from sample codes) */
 
 typedef enum symaccel_status {
     SYMACCEL_OK = 0,
@@ -387,6 +387,44 @@ int symaccel_mpa_polyphase(symaccel_ctx *ctx, int n_frames, const float *h_in, f
 int symaccel_mpa_polyphase_pp_device(symaccel_ctx *ctx, int n_frames, const float *d_in, const float *d_vvec_in,
                                      const int32_t *d_vfront_in, float *d_vvec_out, int32_t *d_vfront_out,
                                      float *d_pcm, size_t n_chains, size_t packets_per_chain);
+
+/* Layer I / Layer II from what the bit reader leaves (Layer1::decode's sample loop and tail, layer1/mod.rs:142-194; Layer2::decode's,
+ * layer2/mod.rs:320-384): dequantisation, scaling and synthesis::synthesis in ONE kernel.  Header, allocation, scale-factor and sample
+ * READING stay with the caller; what crosses the link is 2 bytes per sample plus one record per channel-packet, not f32 sub-band
+ * samples.  Shapes and state are those of symaccel_mpa_polyphase*: n_frames = 12 (Layer I) or 36 (Layer II) samples per sub-band.
+ *   codes[chain][packet][32][n_frames] uint16, sub-band major (the order of samples[ch][n_frames * sb + s]), 8-byte aligned: the raw
+ *       sample codes.  Layer II: the three values of every triplet at [sb][3 * gr + i], a grouped codeword already un-grouped by
+ *       the caller (c % nlevels, c /= nlevels: layer2/mod.rs:176-179).  A code is masked to its width; codes of a sub-band that is
+ *       not allocated are ignored.  An intensity-coded sub-band has the same codes in both channels' planes.
+ *   rec[chain][packet][symaccel_mpa12_record_bytes(layer)]:
+ *       Layer I, 64 bytes:   bits[32] (0 = not allocated, else 2..15: alloc[ch][sb] of layer1/mod.rs:110), scf[32] (0..63)
+ *       Layer II, 128 bytes: qclass[32] (0 = not allocated, else 1 + the index into QUANT_CLASS, layer2/mod.rs:46-64),
+ *                            scf[3][32] (0..63: scalefacs[ch][part][sb] of layer2/mod.rs:313-315)
+ *   status[chain][packet] uint8 (may be NULL): 0, or 1 for a channel-packet whose record is out of range (Layer I bits of 1 or above
+ *       15, qclass above 17, a scale-factor index above 63).  Such a channel-packet is synthesised as if nothing were allocated
+ *       (the filterbank still advances); its neighbours are untouched.  No table is indexed out of range.
+ * Arithmetic (every rounded operation the reference's, in its order; the tables: SYMACCEL_TABLE_MPA12):
+ *   Layer I  (layer1/mod.rs:51-60, 156-159):   a = sign_extend(code ^ 1 << (bits - 1), bits);
+ *                                              x = SCALEFACTORS[scf] * (FACTOR[bits] * (float)(a + 1))
+ *   Layer II (layer2/mod.rs:198-213, 341-346): a likewise with the class's sample width; s = (float)a / 2^(width - 1);
+ *                                              x = SCALEFACTORS[scf[j / 12]] * (c * (s + d)), j = the sample's index in the sub-band
+ * A sub-band that is not allocated is +0.0.  Another layer: SYMACCEL_ERR_UNSUPPORTED; anything else wrong (null or misaligned pointers,
+ * aliased ping-pong state): SYMACCEL_ERR_INVALID_ARG; both before anything is launched. */
+#define SYMACCEL_MPA_LAYER1 1 /* MpegLayer::Layer1: Layer1::decode, layer1/mod.rs:74-197 */
+#define SYMACCEL_MPA_LAYER2 2 /* MpegLayer::Layer2: Layer2::decode, layer2/mod.rs:231-387 */
+/* Bytes of one channel-packet's record: 64 (Layer I), 128 (Layer II), 0 for any other layer.  Pure arithmetic, no context. */
+size_t symaccel_mpa12_record_bytes(int layer);
+/* Layer1::decode / Layer2::decode behind the bit reader (layer1/mod.rs:142-194, layer2/mod.rs:320-384), state in place */
+int symaccel_mpa12_decode_device(symaccel_ctx *ctx, int layer, const uint16_t *d_codes, const uint8_t *d_rec, float *d_vvec_io,
+                                 int32_t *d_vfront_io, float *d_pcm, uint8_t *d_status, size_t n_chains, size_t packets_per_chain);
+/* The same with SynthesisState (layer1/mod.rs:63, layer2/mod.rs:220) as separate in / out buffers (pairwise distinct): one launch */
+int symaccel_mpa12_decode_pp_device(symaccel_ctx *ctx, int layer, const uint16_t *d_codes, const uint8_t *d_rec,
+                                    const float *d_vvec_in, const int32_t *d_vfront_in, float *d_vvec_out, int32_t *d_vfront_out,
+                                    float *d_pcm, uint8_t *d_status, size_t n_chains, size_t packets_per_chain);
+/* The same between host buffers (layer1/mod.rs:142-194, layer2/mod.rs:320-384 for a batch of packets): chunked along the packet
+ * axis, copy-in, kernel and copy-out overlapped, the state carried from chunk to chunk on the device.  h_status may be NULL. */
+int symaccel_mpa12_decode(symaccel_ctx *ctx, int layer, const uint16_t *h_codes, const uint8_t *h_rec, float *h_vvec_io,
+                          int32_t *h_vfront_io, float *h_pcm, uint8_t *h_status, size_t n_chains, size_t packets_per_chain);
 
 /* --------------------------------------------------------------------------------- Vorbis */
 
@@ -824,7 +862,16 @@ int symaccel_adpcm_decode(symaccel_ctx *ctx, const void *h_bytes, size_t block_p
  *                              bringing the kernel's status bytes back: the two rules -- byte k of an MS block above 6, byte 4 k + 2 of an
  *                              IMA WAV block above 88, per channel k -- are stated there and in csrc/adpcm.hip and must stay in step
  *                              (tests/test_batcher_adpcm.py compares the ticket's status with the kernel's)
- * `units_per_chain` = frames (AAC) / granules (MP3) / blocks (Vorbis) / words (FLAC, ALAC) / bytes (ADPCM) per chain.  Two forms:
+ *   SYMACCEL_BATCH_MPA12_DECODE symaccel_mpa12_decode across streams (layer1/mod.rs:142-194, layer2/mod.rs:320-384): a chain is a channel,
+ *                              units_per_chain = packets, param = the layer (SYMACCEL_MPA_LAYER1 / 2): in = { codes[chain][unit][32][n_frames]
+ *                              u16, rec[chain][unit][symaccel_mpa12_record_bytes(layer)] }; state = { vvec[chain][1024], vfront[chain] i32 };
+ *                              out = pcm[chain][unit][32 * n_frames] f32.  Chains are independent, so streams of any channel count share a
+ *                              launch.  A submission holding a record that is out of range (what symaccel_mpa12_decode marks with status
+ *                              1) fails alone with SYMACCEL_ERR_INVALID_ARG and runs as silence (nothing allocated; its state still
+ *                              advances): the batcher reads the records in the page-locked slot when the group is launched (check_mpa12,
+ *                              csrc/batcher.cpp) -- the rule is stated there and in csrc/mpa12_dequant.h and must stay in step
+ *                              (tests/test_batcher_mpa12.py compares the two)
+ * `units_per_chain` = frames (AAC) / granules (MP3) / blocks (Vorbis) / words (FLAC, ALAC) / bytes (ADPCM) / packets (MPA12) per chain.  Two forms:
  *   zero-copy:  reserve() hands out a slot of page-locked staging memory (the front end writes its output straight into the DMA
  *               source), commit() says it is filled, wait() blocks until slot.out / slot.state hold the PCM and the state AFTER
  *               the batch, release() gives the slot back.  Commit a reservation before waiting for anything on the same thread.
@@ -847,6 +894,7 @@ int symaccel_adpcm_decode(symaccel_ctx *ctx, const void *h_bytes, size_t block_p
 #define SYMACCEL_BATCH_FLAC_RESTORE 7
 #define SYMACCEL_BATCH_ALAC_PREDICT 8
 #define SYMACCEL_BATCH_ADPCM_DECODE 9
+#define SYMACCEL_BATCH_MPA12_DECODE 10
 #define SYMACCEL_BATCH_MAX_INPUTS 6
 typedef struct symaccel_batcher symaccel_batcher;
 typedef struct symaccel_batch_slot {
@@ -1056,7 +1104,9 @@ enum symaccel_table {
     SYMACCEL_TABLE_VORBIS_FLOOR1_DB = 6, /* 256, vorbis floor.rs:21-112 */
     SYMACCEL_TABLE_MP3_CONSTS = 7,      /* 264: the hybrid-synthesis / dct32 constants in the kernels' packed order */
     SYMACCEL_TABLE_MP3_POW43 = 8,       /* 8207, requantize.rs:28-31 */
-    SYMACCEL_TABLE_MP3_POW2AB = 9       /* 1346: 2^(0.25 e), e = -1300 .. 45 (requantize.rs:280, 343) */
+    SYMACCEL_TABLE_MP3_POW2AB = 9,      /* 1346: 2^(0.25 e), e = -1300 .. 45 (requantize.rs:280, 343) */
+    SYMACCEL_TABLE_MPA12 = 10           /* 131: FACTOR[16] (layer1/mod.rs:19-47) | LAYER12_SCALEFACTORS[64] (layer12.rs:9-76) | the 17 quantisation
+                                           classes of layer2/mod.rs:46-64 as {c, d, sample width} */
 };
 /* Copies the HOST copy of a constant table; returns the number of floats, or a negative status. */
 int symaccel_table_f32(const symaccel_ctx *ctx, int table, float *dst, size_t capacity);

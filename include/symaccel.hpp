@@ -107,6 +107,13 @@ public:
                       SampleFormat out = SampleFormat::Native, std::uint8_t *h_status = nullptr) {
         check(symaccel_adpcm_decode(ctx_, h_bytes, block_pitch, n_blocks, codec, channels, frames_per_block, h_pcm, static_cast<int>(out), h_status), ctx_);
     }
+    // Layer1::decode / Layer2::decode behind the bit reader (layer1/mod.rs:142-194, layer2/mod.rs:320-384) for n_chains x
+    // packets_per_chain channel-packets in host memory: h_codes[chain][packet][32][n_frames] u16, h_rec[chain][packet][record bytes],
+    // state and PCM as mp3::synthesis takes them; h_status[chain][packet] (may be null): 1 = a record out of range, decoded as silence
+    void mpa12_decode(int layer, const std::uint16_t *h_codes, const std::uint8_t *h_rec, float *h_vvec_io, std::int32_t *h_vfront_io, float *h_pcm,
+                      std::size_t n_chains, std::size_t packets_per_chain, std::uint8_t *h_status = nullptr) {
+        check(symaccel_mpa12_decode(ctx_, layer, h_codes, h_rec, h_vvec_io, h_vfront_io, h_pcm, h_status, n_chains, packets_per_chain), ctx_);
+    }
 
 private:
     symaccel_ctx *ctx_ = nullptr;
@@ -1281,6 +1288,107 @@ private:
     std::vector<symaccel_mp3_side> side_;
 };
 
+// MPEG-1/2 Layer I and Layer II: one packet = one frame = 384 (Layer I) or 1152 (Layer II) frames per channel.  Per channel-packet:
+// what the bit reader leaves -- the raw sample codes, sub-band major, and the allocation / scale-factor record (layer1/mod.rs:101-138,
+// layer2/mod.rs:262-318; include/symaccel.h, symaccel_mpa12_decode) -- handed to the fused kernel, which dequantises, scales and runs the
+// polyphase filterbank (layer1/mod.rs:142-194, layer2/mod.rs:320-384).  Two bytes per sample cross the link instead of four.  Chains are
+// independent (an intensity-coded sub-band simply has the same codes in both channels), so streams of any channel count share a launch.
+struct Mpa12 {
+    using Sample = float;
+    struct Params {
+        int layer = SYMACCEL_MPA_LAYER2;
+        std::size_t channels = 2;
+    };
+    struct Packet {
+        std::uint64_t ts = 0;
+        std::vector<std::uint16_t> codes;  // [channel][32][n_frames]
+        std::vector<std::uint8_t> rec;     // [channel][record bytes]
+    };
+    explicit Mpa12(const Params &p)
+        : layer_(p.layer), nch_(p.channels), nf_(p.layer == SYMACCEL_MPA_LAYER1 ? 12 : 36), rb_(symaccel_mpa12_record_bytes(p.layer)), vvec_(p.channels * 1024, 0.0f),
+          vfront_(p.channels, 0) {
+        if (rb_ == 0) throw Error(Error::Kind::Unsupported, SYMACCEL_ERR_UNSUPPORTED, "mpa: invalid mpeg audio layer");
+        if (nch_ < 1 || nch_ > 2) throw std::invalid_argument("Mpa12: one or two channels");
+    }
+    static std::uint64_t id(const Packet &p) { return p.ts; }
+    std::size_t channels() const { return nch_; }
+    bool device_output_is_final() const { return true; }
+    std::size_t frames_per_packet() const { return 32 * nf_; }
+    std::size_t packet_frames(std::size_t) const { return 32 * nf_; }
+    std::size_t plane_offset(std::size_t c, std::size_t i, std::size_t k) const { return (c * k + i) * 32 * nf_; }
+    void reset_state() {  // MpaDecoder::reset: fresh State (SynthesisState::default(), decoder.rs:152-155)
+        std::fill(vvec_.begin(), vvec_.end(), 0.0f);
+        std::fill(vfront_.begin(), vfront_.end(), 0);
+    }
+    void decode_batch(Context &ctx, const std::vector<Packet> &batch, std::vector<float> &pcm) {
+        const std::size_t k = batch.size();
+        codes_.resize(nch_ * k * 32 * nf_);
+        rec_.resize(nch_ * k * rb_);
+        status_.assign(nch_ * k, 0);
+        pcm.resize(nch_ * k * 32 * nf_);
+        const BatchView v{codes_.data(), rec_.data(), k, nf_, rb_};
+        for (std::size_t i = 0; i < k; ++i) put(v, i, batch[i]);
+        ctx.mpa12_decode(layer_, codes_.data(), rec_.data(), vvec_.data(), vfront_.data(), pcm.data(), nch_, k, status_.data());
+        for (std::uint8_t st : status_)
+            if (st) throw std::invalid_argument("Mpa12: a record is out of range");  // (what the batcher's ticket says: SYMACCEL_ERR_INVALID_ARG)
+    }
+    static constexpr int kBatchKind = SYMACCEL_BATCH_MPA12_DECODE;
+    static constexpr bool kDirect = true;
+    void attach(Batcher &) {}
+    int batch_param() const { return layer_; }
+    std::size_t units_per_packet() const { return 1; }
+    std::size_t batch_chains(std::size_t) const { return nch_; }
+    std::size_t batch_units(std::size_t k) const { return k; }
+    struct BatchView {  // packet i of channel c is unit i of chain c
+        std::uint16_t *codes = nullptr;
+        std::uint8_t *rec = nullptr;
+        std::size_t k = 0, nf = 0, rb = 0;
+        std::uint16_t *codes_of(std::size_t c, std::size_t i) const { return codes + (c * k + i) * 32 * nf; }
+        std::uint8_t *rec_of(std::size_t c, std::size_t i) const { return rec + (c * k + i) * rb; }
+    };
+    BatchView view(const symaccel_batch_slot &slot, std::size_t k) const {
+        return BatchView{static_cast<std::uint16_t *>(slot.input[0]), static_cast<std::uint8_t *>(slot.input[1]), k, nf_, rb_};
+    }
+    void put(const BatchView &v, std::size_t i, const Packet &p) const {
+        if (p.codes.size() != nch_ * 32 * nf_ || p.rec.size() != nch_ * rb_) throw std::invalid_argument("Mpa12: packet shape");
+        for (std::size_t c = 0; c < nch_; ++c) {
+            std::copy_n(p.codes.data() + c * 32 * nf_, 32 * nf_, v.codes_of(c, i));
+            std::copy_n(p.rec.data() + c * rb_, rb_, v.rec_of(c, i));
+        }
+    }
+    Packet extract(const BatchView &v, std::size_t i) const {
+        Packet p;
+        p.codes.resize(nch_ * 32 * nf_);
+        p.rec.resize(nch_ * rb_);
+        for (std::size_t c = 0; c < nch_; ++c) {
+            std::copy_n(v.codes_of(c, i), 32 * nf_, p.codes.data() + c * 32 * nf_);
+            std::copy_n(v.rec_of(c, i), rb_, p.rec.data() + c * rb_);
+        }
+        return p;
+    }
+    void put_state(const symaccel_batch_slot &slot) const {
+        std::memcpy(slot.state[0], vvec_.data(), vvec_.size() * sizeof(float));
+        std::memcpy(slot.state[1], vfront_.data(), vfront_.size() * sizeof(std::int32_t));
+    }
+    void fill_slot(const std::vector<Packet> &batch, const symaccel_batch_slot &slot) {
+        const BatchView v = view(slot, batch.size());
+        for (std::size_t i = 0; i < batch.size(); ++i) put(v, i, batch[i]);
+        put_state(slot);
+    }
+    void take_state(const symaccel_batch_slot &slot) {
+        std::memcpy(vvec_.data(), slot.state[0], vvec_.size() * sizeof(float));
+        std::memcpy(vfront_.data(), slot.state[1], vfront_.size() * sizeof(std::int32_t));
+    }
+
+private:
+    int layer_;
+    std::size_t nch_, nf_, rb_;
+    std::vector<float> vvec_;
+    std::vector<std::int32_t> vfront_;
+    std::vector<std::uint16_t> codes_;
+    std::vector<std::uint8_t> rec_, status_;
+};
+
 // The same Layer III packets one stage earlier: what the entropy decoder produces (layer3/mod.rs:393-420) -- the Huffman samples as
 // int16, the GranuleChannel fields requantize reads, one stereo record per granule for a two-channel stream -- handed to
 // symaccel_mp3_decode_pipelined, which runs requantize + joint stereo + the synthesis tail on the device (layer3/mod.rs:421-477).
@@ -1853,6 +1961,8 @@ inline void register_enabled_codecs(CodecRegistry &registry) {
 }
 // ... and ADPCM, entered by a call of its own (the shim's `adpcm::register`): the list above is the one the shim's `register()` has
 inline void register_adpcm(CodecRegistry &registry) { registry.register_audio_decoder<Adpcm>(); }
+// ... and MPEG Layer I / II (CODEC_ID_MP1 / CODEC_ID_MP2), likewise
+inline void register_mpa12(CodecRegistry &registry) { registry.register_audio_decoder<Mpa12>(); }
 
 }  // namespace codecs
 

@@ -23,7 +23,7 @@ ERR_DECODE = -5
 
 TABLE_AAC_KBD_LONG, TABLE_AAC_KBD_SHORT, TABLE_AAC_SINE_LONG, TABLE_AAC_SINE_SHORT = 0, 1, 2, 3
 TABLE_MP3_SYNTH_D, TABLE_MP3_IMDCT_WIN, TABLE_VORBIS_FLOOR1_DB, TABLE_MP3_CONSTS = 4, 5, 6, 7
-TABLE_MP3_POW43, TABLE_MP3_POW2AB = 8, 9
+TABLE_MP3_POW43, TABLE_MP3_POW2AB, TABLE_MPA12 = 8, 9, 10
 
 # SYMACCEL_FMT_*: the sample formats PCM can be delivered in (symaccel_pcm_convert)
 FMT_U8, FMT_S8, FMT_U16, FMT_S16, FMT_U24, FMT_S24, FMT_U32, FMT_S32, FMT_F32 = range(1, 10)
@@ -66,6 +66,7 @@ ABI_SYMBOLS = [
     "symaccel_batcher_reserve_fmt", "symaccel_batcher_submit_fmt",
     "symaccel_adpcm_block_bytes", "symaccel_adpcm_decode_device", "symaccel_adpcm_decode",
     "symaccel_batcher_submit_adpcm_decode",
+    "symaccel_mpa12_record_bytes", "symaccel_mpa12_decode_device", "symaccel_mpa12_decode_pp_device", "symaccel_mpa12_decode",
 ]
 
 _vp, _sz, _i, _d, _u32 = C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.c_uint32
@@ -246,6 +247,11 @@ class Library:
         d.symaccel_adpcm_block_bytes.restype = _sz
         d.symaccel_adpcm_decode_device.argtypes = [_vp, _vp, _sz, _sz, _i, _sz, _sz, _vp, _i, _vp]
         d.symaccel_adpcm_decode.argtypes = [_vp, _vp, _sz, _sz, _i, _sz, _sz, _vp, _i, _vp]
+        d.symaccel_mpa12_record_bytes.argtypes = [_i]
+        d.symaccel_mpa12_record_bytes.restype = _sz
+        d.symaccel_mpa12_decode_device.argtypes = [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz]
+        d.symaccel_mpa12_decode_pp_device.argtypes = [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz]
+        d.symaccel_mpa12_decode.argtypes = [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz]
         d.symaccel_alac_block_status_device.argtypes = [_vp, _vp, _sz, _vp]
         d.symaccel_vorbis_floor1_status_device.argtypes = [_vp, _i, _vp, _sz, _vp]
         d.symaccel_aac_tns_status_device.argtypes = [_vp, _sz, _vp, _sz, _vp]

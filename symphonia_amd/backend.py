@@ -381,6 +381,47 @@ class MpaPolyphase:
         return res, vv, vf
 
 
+MPA_LAYER1, MPA_LAYER2 = 1, 2  # SYMACCEL_MPA_LAYER*
+
+
+class Mpa12Decode:
+    """Layer I / Layer II behind the bit reader (layer1/mod.rs:142-194, layer2/mod.rs:320-384): 16-bit sample codes and one
+    record per channel-packet in, dequantised, scaled and synthesised in one kernel (symaccel_mpa12_decode*)."""
+
+    def __init__(self, ctx, layer):
+        if layer not in (MPA_LAYER1, MPA_LAYER2):
+            raise ValueError("layer must be 1 or 2 (Layer III: Mp3Synthesis.decode)")
+        self.ctx, self.layer = ctx, int(layer)
+        self.n_frames = 12 if layer == MPA_LAYER1 else 36
+        self.record_bytes = int(ctx.lib.dll.symaccel_mpa12_record_bytes(self.layer))
+
+    def decode(self, codes, rec, v_vec, v_front, pcm=None, state_out=None, status=None):
+        """codes[chains, packets, 32, n_frames] u16 (sub-band major), rec[chains, packets, record_bytes] u8; state as
+        MpaPolyphase.synth takes it; status[chains, packets] u8 (optional for device buffers).
+        numpy: returns (pcm, v_vec, v_front, status); torch: state updated in place (or written to state_out), returns pcm."""
+        d = self.ctx.lib.dll
+        nch, npk = int(codes.shape[0]), int(codes.shape[1])
+        assert tuple(codes.shape[2:]) == (32, self.n_frames) and tuple(rec.shape) == (nch, npk, self.record_bytes)
+        if _is_torch(codes):
+            import torch
+            if pcm is None:
+                pcm = torch.empty((nch, npk, 32 * self.n_frames), dtype=torch.float32, device=codes.device)
+            if state_out is not None:
+                self.ctx._call(d.symaccel_mpa12_decode_pp_device, self.layer, _ptr(codes), _ptr(rec), _ptr(v_vec), _ptr(v_front),
+                               _ptr(state_out[0]), _ptr(state_out[1]), _ptr(pcm), _ptr(status), nch, npk)
+                return pcm
+            self.ctx._call(d.symaccel_mpa12_decode_device, self.layer, _ptr(codes), _ptr(rec), _ptr(v_vec), _ptr(v_front), _ptr(pcm),
+                           _ptr(status), nch, npk)
+            return pcm
+        c, r = _np(codes, np.uint16), _np(rec, np.uint8)
+        vv = np.array(v_vec, dtype=np.float32, copy=True, order="C")
+        vf = np.array(v_front, dtype=np.int32, copy=True, order="C")
+        res = np.empty((nch, npk, 32 * self.n_frames), dtype=np.float32)
+        st = np.zeros((nch, npk), dtype=np.uint8)
+        self.ctx._call(d.symaccel_mpa12_decode, self.layer, _ptr(c), _ptr(r), _ptr(vv), _ptr(vf), _ptr(res), _ptr(st), nch, npk)
+        return res, vv, vf, st
+
+
 MP3_REQUANT_DTYPE = np.dtype([("global_gain", np.uint8), ("flags", np.uint8), ("block_type", np.uint8),
                               ("is_mixed", np.uint8), ("subblock_gain", np.uint8, (3,)), ("reserved", np.uint8),
                               ("rzero", np.uint16), ("scalefacs", np.uint8, (39,)), ("pad", np.uint8, (3,))])
@@ -945,6 +986,7 @@ class PinnedBuffer:
 BATCH_AAC_SYNTH, BATCH_MP3_SYNTH, BATCH_MP3_DECODE, BATCH_VORBIS_SYNTH, BATCH_AAC_DECODE = 1, 2, 3, 4, 5
 BATCH_VORBIS_DECODE, BATCH_FLAC_RESTORE, BATCH_ALAC_PREDICT = 6, 7, 8
 BATCH_ADPCM_DECODE = 9
+BATCH_MPA12_DECODE = 10
 BATCH_MAX_INPUTS = 6
 
 

@@ -143,6 +143,18 @@ bool plane_sizes(int kind, int param, size_t units, PlaneSizes *ps) {
         ps->out = (size_t)ap.nch * fpb * (ap.fmt ? symaccel_sample_bytes(ap.fmt) : 4);
         return true;
     }
+    case SYMACCEL_BATCH_MPA12_DECODE: {  // symaccel_mpa12_decode: codes, rec | vvec, vfront | pcm; param = the layer
+        const size_t nf = (size_t)mpa12_n_frames(param);
+        if (nf == 0 || units > 0x3fffffffu) return false;
+        ps->n_in = 2;
+        ps->in[0] = units * 32 * nf * 2;
+        ps->in[1] = units * symaccel_mpa12_record_bytes(param);
+        ps->n_state = 2;
+        ps->state[0] = 4096;
+        ps->state[1] = 4;
+        ps->out = units * 32 * nf * 4;
+        return true;
+    }
     default: return false;
     }
 }
@@ -461,6 +473,21 @@ int check_adpcm(size_t units, int param, const TicketView &v) {
     return SYMACCEL_OK;
 }
 
+// An MPA12_DECODE submission: SYMACCEL_ERR_INVALID_ARG if any of its records is one the kernel marks with status 1 (Mpa12Lane::out_of_range,
+// csrc/mpa12_dequant.h: Layer I bits of 1 or above 15, a class above 17, a scale-factor index above 63).  Such a submission runs as
+// silence: its records are cleared in the slot, so every channel-packet of it allocates nothing and the filterbank alone advances.
+int check_mpa12(size_t units, int param, TicketView &v) {
+    const size_t rb = symaccel_mpa12_record_bytes(param);
+    uint8_t *r = v.in<uint8_t>(1);
+    bool bad = false;
+    for (size_t k = 0; k < v.n_chains * units && !bad; ++k, r += rb)
+        for (size_t i = 0; i < rb && !bad; ++i)
+            bad = i >= 32 ? r[i] > 63 : (param == SYMACCEL_MPA_LAYER1 ? r[i] == 1 || r[i] > 15 : r[i] > (uint8_t)kMpa12Classes);
+    if (!bad) return SYMACCEL_OK;
+    std::memset(v.slot + v.lay.in[1], 0, v.lay.in_bytes[1]);
+    return SYMACCEL_ERR_INVALID_ARG;
+}
+
 // Per-ticket facts, computed once in front of the first chunk: the slot's layout; Vorbis: what every chain's flags account for (the
 // state planes they depend on are overwritten by the scatter of the ticket's chunk -- gather, scatter and out_valid all read these).
 // Submissions with an output format (symaccel_batcher_reserve_fmt) leave as converting pieces, a frame range of one interleave group
@@ -500,6 +527,7 @@ void validate_and_count(Group *g) {
         if (g->kind == SYMACCEL_BATCH_FLAC_RESTORE) v.status = check_flac(g->units, g->param, v);
         if (g->kind == SYMACCEL_BATCH_ALAC_PREDICT) v.status = check_alac(g->param, v);
         if (g->kind == SYMACCEL_BATCH_ADPCM_DECODE) v.status = check_adpcm(g->units, g->param, v);
+        if (g->kind == SYMACCEL_BATCH_MPA12_DECODE) v.status = check_mpa12(g->units, g->param, v);
         if (v.status == SYMACCEL_OK) v.status = v.fmt_status;
     }
     // FLAC / ALAC: the device plane's rows at the pitch the lane-per-block kernels run fastest at (symaccel_row_stride: rows 4 / 8 / 16 / 32 KiB apart -- the
@@ -686,6 +714,9 @@ int launch_chunk(symaccel_ctx *ctx, Group *g, const Chunk &ch) {
         return launch_adpcm_decode(ctx, ctx->stream, in[0], g->units, ch.nc, ap.codec, (unsigned)ap.nch,
                                    (unsigned)adpcm_frames_of_bytes(ap.codec, (size_t)ap.nch, g->units), ch.out, ap.fmt, nullptr);
     }
+    case SYMACCEL_BATCH_MPA12_DECODE:  // layer1/mod.rs:142-194, layer2/mod.rs:320-384 (no status plane: check_mpa12 judged the records)
+        return launch_mpa12_decode(ctx, g->param, (const uint16_t *)in[0], (const uint8_t *)in[1], nullptr, (const float *)si[0], (const int32_t *)si[1],
+                                   (float *)so[0], (int32_t *)so[1], (float *)ch.out, ch.nc, g->units);
     default: return SYMACCEL_ERR_INVALID_ARG;
     }
 }

@@ -207,6 +207,7 @@ int upload_tables(symaccel_ctx *ctx) {
     UP(mp3_pow2ab, t.mp3_pow2ab, sizeof t.mp3_pow2ab);
     UP(mp3_band_map, t.mp3_band_map, sizeof t.mp3_band_map);
     UP(mp3_is_ratios, t.mp3_is_ratios, sizeof t.mp3_is_ratios);
+    UP(mpa12, t.mpa12, sizeof t.mpa12);
 #undef UP
     return SYMACCEL_OK;
 }
@@ -1390,6 +1391,40 @@ int symaccel_mpa_polyphase(symaccel_ctx *ctx, int n_frames, const float *h_in, f
     return symaccel_sync(ctx);
 }
 
+size_t symaccel_mpa12_record_bytes(int layer) { return layer == SYMACCEL_MPA_LAYER1 ? 64 : layer == SYMACCEL_MPA_LAYER2 ? 128 : 0; }
+
+int symaccel_mpa12_decode_pp_device(symaccel_ctx *ctx, int layer, const uint16_t *d_codes, const uint8_t *d_rec, const float *d_vvec_in,
+                                    const int32_t *d_vfront_in, float *d_vvec_out, int32_t *d_vfront_out, float *d_pcm,
+                                    uint8_t *d_status, size_t n_chains, size_t packets_per_chain) {
+    if (!ctx) return SYMACCEL_ERR_INVALID_ARG;
+    if (mpa12_n_frames(layer) == 0) return SYMACCEL_ERR_UNSUPPORTED;  // Layer III: symaccel_mp3_decode_*
+    if (n_chains == 0 || packets_per_chain == 0) return SYMACCEL_OK;
+    if (!d_codes || !d_rec || !d_vvec_in || !d_vfront_in || !d_vvec_out || !d_vfront_out || !d_pcm) return SYMACCEL_ERR_INVALID_ARG;
+    if (d_vvec_in == d_vvec_out || d_vfront_in == d_vfront_out || (uintptr_t)d_codes % 8 != 0) return SYMACCEL_ERR_INVALID_ARG;
+    DeviceGuard dev(ctx);
+    if (!dev.ok()) return dev.status();
+    return launch_mpa12_decode(ctx, layer, d_codes, d_rec, d_status, d_vvec_in, d_vfront_in, d_vvec_out, d_vfront_out, d_pcm, n_chains,
+                               packets_per_chain);
+}
+
+int symaccel_mpa12_decode_device(symaccel_ctx *ctx, int layer, const uint16_t *d_codes, const uint8_t *d_rec, float *d_vvec_io,
+                                 int32_t *d_vfront_io, float *d_pcm, uint8_t *d_status, size_t n_chains, size_t packets_per_chain) {
+    if (!ctx) return SYMACCEL_ERR_INVALID_ARG;
+    if (mpa12_n_frames(layer) == 0) return SYMACCEL_ERR_UNSUPPORTED;
+    if (n_chains == 0 || packets_per_chain == 0) return SYMACCEL_OK;
+    if (!d_codes || !d_rec || !d_vvec_io || !d_vfront_io || !d_pcm || (uintptr_t)d_codes % 8 != 0) return SYMACCEL_ERR_INVALID_ARG;
+    DeviceGuard dev(ctx);
+    if (!dev.ok()) return dev.status();
+    const size_t vv_bytes = n_chains * 1024 * 4, vf_bytes = n_chains * 4;
+    void *scratch = nullptr;
+    SYM_TRY(ctx_scratch(ctx, vv_bytes + vf_bytes, &scratch));
+    float *vv_out = (float *)scratch;
+    int32_t *vf_out = (int32_t *)(vv_out + n_chains * 1024);
+    SYM_TRY(launch_mpa12_decode(ctx, layer, d_codes, d_rec, d_status, d_vvec_io, d_vfront_io, vv_out, vf_out, d_pcm, n_chains,
+                                packets_per_chain));
+    return launch_state_copy(ctx, d_vvec_io, vv_out, vv_bytes, d_vfront_io, vf_out, vf_bytes, nullptr, nullptr, 0);
+}
+
 int symaccel_alac_predict_device(symaccel_ctx *ctx, int32_t *d_buf, const symaccel_alac_desc *d_desc,
                                  const int32_t *d_coeffs, size_t n_blocks, size_t blocksize) {
     if (!ctx || blocksize > 0xffffffffu) return SYMACCEL_ERR_INVALID_ARG;
@@ -1486,6 +1521,7 @@ int symaccel_table_f32(const symaccel_ctx *, int table, float *dst, size_t capac
         case SYMACCEL_TABLE_VORBIS_FLOOR1_DB: src = t.vorbis_floor1_db; n = 256; break;
         case SYMACCEL_TABLE_MP3_POW43: src = t.mp3_pow43; n = 8207; break;
         case SYMACCEL_TABLE_MP3_POW2AB: src = t.mp3_pow2ab; n = kMp3Pow2abLen; break;
+        case SYMACCEL_TABLE_MPA12: src = t.mpa12; n = MPA12_TOTAL; break;
         case SYMACCEL_TABLE_MP3_CONSTS: {
             static const std::vector<float> mc = pack_mp3_consts(t);
             src = mc.data();

@@ -7,17 +7,25 @@
 // slot for the dct32s (LDS transpose, row stride 36, conflict-free b128), lane = output sample i for the 512-tap
 // window with the V entries of the previous 16 slots in registers.  One packet (12 or 36 slots) per round; segments
 // start with ceil(16 / n_frames) halo packets that only rebuild the V history.
+//
+// FUSED: the packet arrives as the bit reader leaves it -- 16-bit sample codes plus one record per channel-packet -- and the
+// kernel dequantises and scales on load (mpa12_dequant.h: layer1/mod.rs:51-60, 156-159; layer2/mod.rs:198-213, 341-346).  Lane =
+// sub-band already, so a lane keeps its allocation and scale factors in registers for the whole packet; everything behind the
+// load is the unfused kernel.
 #include "mp3_common.h"
+#include "mpa12_dequant.h"
 
 namespace symaccel {
 
 namespace {
 
-template <int NF>
+// in: FUSED ? codes[chain][packet][32][NF] u16 : in[chain][packet][32 * NF] f32.  rec / status: FUSED only (status may be null).
+template <int NF, bool FUSED>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void mpa_polyphase_kernel(
-    DevTables tb, const float *__restrict__ in, const float *__restrict__ vvec_in, const int32_t *__restrict__ vfront_in,
-    float *__restrict__ vvec_out, int32_t *__restrict__ vfront_out, float *__restrict__ pcm, unsigned n_chains,
-    unsigned packets_per_chain, unsigned seg_len, unsigned segs_per_chain) {
+    DevTables tb, const void *__restrict__ in, const uint8_t *__restrict__ rec, uint8_t *__restrict__ status,
+    const float *__restrict__ vvec_in, const int32_t *__restrict__ vfront_in, float *__restrict__ vvec_out,
+    int32_t *__restrict__ vfront_out, float *__restrict__ pcm, unsigned n_chains, unsigned packets_per_chain, unsigned seg_len,
+    unsigned segs_per_chain) {
     constexpr int kPacket = 32 * NF;                       // floats per channel-packet
     constexpr int kHalo = (kHistOld + NF - 1) / NF;        // packets that rebuild the 16-slot history
     constexpr int kTile = 2 * kPacket, kS = 2 * NF * kSStride;
@@ -71,21 +79,47 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
         const long p = p_first + r;
         const bool active = live && p < p_stop;
         const bool emit = active && p >= (long)p_begin;
-        // ---- packet -> LDS (16 B per lane, coalesced), then lane sb takes its NF consecutive slots
-        if (active) {
-            const float4 *src = reinterpret_cast<const float4 *>(in + (chain_base + (size_t)p) * kPacket);
-            float4 *t4 = reinterpret_cast<float4 *>(tile);
-#pragma unroll
-            for (int q = 0; q < kPacket / 128; ++q) t4[hl + 32 * q] = src[hl + 32 * q];
-        }
-        wave_sync();
         float y[NF];
-        {
+        if constexpr (!FUSED) {
+            // ---- packet -> LDS (16 B per lane, coalesced), then lane sb takes its NF consecutive slots
+            if (active) {
+                const float4 *src = reinterpret_cast<const float4 *>(static_cast<const float *>(in) + (chain_base + (size_t)p) * kPacket);
+                float4 *t4 = reinterpret_cast<float4 *>(tile);
+#pragma unroll
+                for (int q = 0; q < kPacket / 128; ++q) t4[hl + 32 * q] = src[hl + 32 * q];
+            }
+            wave_sync();
             const float4 *t4 = reinterpret_cast<const float4 *>(tile + NF * hl);  // NF * 4 B lane stride: conflict-free b128
 #pragma unroll
             for (int k = 0; k < NF / 4; ++k) {
                 const float4 v = t4[k];
                 y[4 * k] = v.x; y[4 * k + 1] = v.y; y[4 * k + 2] = v.z; y[4 * k + 3] = v.w;
+            }
+        } else {
+            // ---- codes -> LDS (8 B per lane, coalesced) and the lane's record bytes; then lane sb takes its NF codes
+            Mpa12Lane<NF> ln;
+            if (active) {
+                const uint2 *src = reinterpret_cast<const uint2 *>(static_cast<const uint16_t *>(in) + (chain_base + (size_t)p) * kPacket);
+                uint2 *t2 = reinterpret_cast<uint2 *>(tile);
+#pragma unroll
+                for (int q = 0; q < kPacket / 128; ++q) t2[hl + 32 * q] = src[hl + 32 * q];
+                ln.load(rec + (chain_base + (size_t)p) * Mpa12Lane<NF>::kRecBytes, hl);
+            }
+            // a record out of range anywhere in the channel-packet: status 1, and the packet runs as all-unallocated
+            const unsigned long long bad_lanes = __ballot(ln.out_of_range());
+            const bool bad = (unsigned)(bad_lanes >> (32 * half)) != 0u;
+            if (bad) ln.alloc = 0;
+            if (emit && hl == 0 && status) status[chain_base + (size_t)p] = bad ? 1 : 0;
+            ln.lookup(tb.mpa12);
+            wave_sync();
+            const uint2 *c2 = reinterpret_cast<const uint2 *>(reinterpret_cast<const uint16_t *>(tile) + NF * hl);  // NF * 2 B lane stride
+#pragma unroll
+            for (int k = 0; k < NF / 4; ++k) {
+                const uint2 v = c2[k];
+                y[4 * k] = ln.dequant(v.x & 0xffffu, 4 * k);
+                y[4 * k + 1] = ln.dequant(v.x >> 16, 4 * k + 1);
+                y[4 * k + 2] = ln.dequant(v.y & 0xffffu, 4 * k + 2);
+                y[4 * k + 3] = ln.dequant(v.y >> 16, 4 * k + 3);
             }
         }
         wave_sync();  // every lane has read its run; the buffer becomes S[slot][sb]
@@ -160,9 +194,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
 
 }  // namespace
 
-int launch_mpa_polyphase(symaccel_ctx *ctx, int n_frames, const float *d_in, const float *d_vvec_in,
-                         const int32_t *d_vfront_in, float *d_vvec_out, int32_t *d_vfront_out, float *d_pcm, size_t n_chains,
-                         size_t packets_per_chain) {
+namespace {
+
+template <bool FUSED>
+int launch(symaccel_ctx *ctx, int n_frames, const void *d_in, const uint8_t *d_rec, uint8_t *d_status, const float *d_vvec_in,
+           const int32_t *d_vfront_in, float *d_vvec_out, int32_t *d_vfront_out, float *d_pcm, size_t n_chains, size_t packets_per_chain) {
     if (packets_per_chain > 0x3fffffffu || n_chains > 0x3fffffffu) return SYMACCEL_ERR_INVALID_ARG;
     const unsigned halo = n_frames == 12 ? 2u : 1u;
     const unsigned seg = choose_segment(ctx, n_chains, packets_per_chain, 8, 2, halo, halo);
@@ -171,18 +207,34 @@ int launch_mpa_polyphase(symaccel_ctx *ctx, int n_frames, const float *d_in, con
     const size_t grid = (items + 1) / 2;
     if (grid > 0x7fffffffu) return SYMACCEL_ERR_INVALID_ARG;
     if (n_frames == 12) {
-        hipLaunchKernelGGL(mpa_polyphase_kernel<12>, dim3((unsigned)grid), dim3(64), 0, ctx->stream, ctx->dev, d_in, d_vvec_in,
-                           d_vfront_in, d_vvec_out, d_vfront_out, d_pcm, (unsigned)n_chains, (unsigned)packets_per_chain, seg,
+        hipLaunchKernelGGL((mpa_polyphase_kernel<12, FUSED>), dim3((unsigned)grid), dim3(64), 0, ctx->stream, ctx->dev, d_in, d_rec, d_status,
+                           d_vvec_in, d_vfront_in, d_vvec_out, d_vfront_out, d_pcm, (unsigned)n_chains, (unsigned)packets_per_chain, seg,
                            (unsigned)segs);
     } else if (n_frames == 36) {
-        hipLaunchKernelGGL(mpa_polyphase_kernel<36>, dim3((unsigned)grid), dim3(64), 0, ctx->stream, ctx->dev, d_in, d_vvec_in,
-                           d_vfront_in, d_vvec_out, d_vfront_out, d_pcm, (unsigned)n_chains, (unsigned)packets_per_chain, seg,
+        hipLaunchKernelGGL((mpa_polyphase_kernel<36, FUSED>), dim3((unsigned)grid), dim3(64), 0, ctx->stream, ctx->dev, d_in, d_rec, d_status,
+                           d_vvec_in, d_vfront_in, d_vvec_out, d_vfront_out, d_pcm, (unsigned)n_chains, (unsigned)packets_per_chain, seg,
                            (unsigned)segs);
     } else {
         return SYMACCEL_ERR_UNSUPPORTED;
     }
     SYM_GPU(ctx, hipGetLastError());
     return SYMACCEL_OK;
+}
+
+}  // namespace
+
+int launch_mpa_polyphase(symaccel_ctx *ctx, int n_frames, const float *d_in, const float *d_vvec_in,
+                         const int32_t *d_vfront_in, float *d_vvec_out, int32_t *d_vfront_out, float *d_pcm, size_t n_chains,
+                         size_t packets_per_chain) {
+    return launch<false>(ctx, n_frames, d_in, nullptr, nullptr, d_vvec_in, d_vfront_in, d_vvec_out, d_vfront_out, d_pcm, n_chains,
+                         packets_per_chain);
+}
+
+int launch_mpa12_decode(symaccel_ctx *ctx, int layer, const uint16_t *d_codes, const uint8_t *d_rec, uint8_t *d_status,
+                        const float *d_vvec_in, const int32_t *d_vfront_in, float *d_vvec_out, int32_t *d_vfront_out, float *d_pcm,
+                        size_t n_chains, size_t packets_per_chain) {
+    return launch<true>(ctx, mpa12_n_frames(layer), d_codes, d_rec, d_status, d_vvec_in, d_vfront_in, d_vvec_out, d_vfront_out, d_pcm,
+                        n_chains, packets_per_chain);
 }
 
 }  // namespace symaccel

@@ -512,6 +512,45 @@ int symaccel_adpcm_decode(symaccel_ctx *ctx, const void *h_bytes, size_t block_p
         });
 }
 
+// symaccel_mpa12_decode_pp_device between host buffers: chunks of whole packets; the synthesis state ping-pongs on the device.
+int symaccel_mpa12_decode(symaccel_ctx *ctx, int layer, const uint16_t *h_codes, const uint8_t *h_rec, float *h_vvec_io, int32_t *h_vfront_io,
+                          float *h_pcm, uint8_t *h_status, size_t n_chains, size_t packets_per_chain) {
+    if (!ctx) return SYMACCEL_ERR_INVALID_ARG;
+    const size_t nf = (size_t)mpa12_n_frames(layer), rb = symaccel_mpa12_record_bytes(layer);
+    if (nf == 0) return SYMACCEL_ERR_UNSUPPORTED;
+    if (n_chains == 0 || packets_per_chain == 0) return SYMACCEL_OK;
+    if (!h_codes || !h_rec || !h_vvec_io || !h_vfront_io || !h_pcm) return SYMACCEL_ERR_INVALID_ARG;
+    if (n_chains > 0x3fffffffu || packets_per_chain > 0x3fffffffu) return SYMACCEL_ERR_INVALID_ARG;
+    const size_t cb = 32 * nf * 2, pb = 32 * nf * 4;  // bytes of one channel-packet's codes / PCM
+    const size_t cp = pick_chunk(packets_per_chain, n_chains * (cb + rb), 0, 8);
+    Pipe pp(ctx);
+    SYM_TRY(pp.init());
+    uint8_t *d_codes[2], *d_rec[2], *d_out[2], *d_st[2];
+    pp.alloc2(d_codes, n_chains * cp * cb);
+    pp.alloc2(d_rec, n_chains * cp * rb);
+    pp.alloc2(d_out, n_chains * cp * pb);
+    pp.alloc2(d_st, n_chains * cp);
+    const State st(pp, {{h_vvec_io, n_chains * Mp3State::kVvec}, {h_vfront_io, n_chains * Mp3State::kVfront}});
+    SYM_TRY(pp.commit());
+    return run_chunks(pp, packets_per_chain, cp, false, &st,
+        [&](int b, size_t p0, size_t np) -> int {
+            SYM_TRY(copy_rows(ctx, d_codes[b], np * cb, reinterpret_cast<const uint8_t *>(h_codes) + p0 * cb, packets_per_chain * cb, np * cb, n_chains,
+                              hipMemcpyHostToDevice, pp.s_in));
+            return copy_rows(ctx, d_rec[b], np * rb, h_rec + p0 * rb, packets_per_chain * rb, np * rb, n_chains, hipMemcpyHostToDevice, pp.s_in);
+        },
+        [&](size_t k, int b, size_t np) {
+            char *si = static_cast<char *>(st.in(k)), *so = static_cast<char *>(st.out(k));
+            return launch_mpa12_decode(ctx, layer, (const uint16_t *)d_codes[b], d_rec[b], d_st[b], (const float *)si,
+                                       (const int32_t *)(si + n_chains * Mp3State::kVvec), (float *)so, (int32_t *)(so + n_chains * Mp3State::kVvec),
+                                       (float *)d_out[b], n_chains, np);
+        },
+        [&](int b, size_t p0, size_t np) -> int {
+            SYM_TRY(copy_rows(ctx, h_pcm + p0 * 32 * nf, packets_per_chain * pb, d_out[b], np * pb, np * pb, n_chains, hipMemcpyDeviceToHost, pp.s_out));
+            if (h_status) SYM_TRY(copy_rows(ctx, h_status + p0, packets_per_chain, d_st[b], np, np, n_chains, hipMemcpyDeviceToHost, pp.s_out));
+            return SYMACCEL_OK;
+        });
+}
+
 int symaccel_flac_restore_pipelined(symaccel_ctx *ctx, int32_t *h_buf, const symaccel_flac_desc *h_desc, const int32_t *h_coeffs,
                                     size_t n_blocks, size_t blocksize, size_t chunk_blocks) {
     if (!ctx || blocksize > 65535) return SYMACCEL_ERR_INVALID_ARG;

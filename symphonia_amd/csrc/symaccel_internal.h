@@ -49,6 +49,8 @@ struct HostTables {
     float mp3_is_ratios[7 + 64][2];   // INTENSITY_STEREO_RATIOS_MPEG1[7] | _MPEG2[2][32] as (left, right) (stereo.rs:31-118)
     // Vorbis (floor.rs:21-112)
     float vorbis_floor1_db[256];
+    // MPEG Layer I / II dequantisation, packed as Mpa12Layout (layer1/mod.rs:19-47, layer12.rs:9-76, layer2/mod.rs:46-64)
+    float mpa12[131];
 };
 
 const HostTables &host_tables();
@@ -72,6 +74,7 @@ struct DevTables {
     const float *mp3_pow43, *mp3_pow2ab;
     const uint8_t *mp3_band_map;         // [9][4][576]
     const float *mp3_is_ratios;          // [71][2]
+    const float *mpa12;                  // packed, see Mpa12Layout
 };
 
 // Offsets (in floats) inside DevTables::mp3_consts.
@@ -91,6 +94,17 @@ enum Mp3ConstLayout {
     MP3C_SYNTH_D = 264,    // 512
     MP3C_TOTAL = 776
 };
+
+// Offsets (in floats) inside HostTables::mpa12 / DevTables::mpa12 (SYMACCEL_TABLE_MPA12).
+constexpr int kMpa12Classes = 17;  // QUANT_CLASS, layer2/mod.rs:46-64
+enum Mpa12Layout {
+    MPA12_FACTOR = 0,   // 16: FACTOR[bits], entries 0 and 1 are 0.0 (layer1/mod.rs:19-47)
+    MPA12_SCF = 16,     // 64: LAYER12_SCALEFACTORS (layer12.rs:9-76)
+    MPA12_CLASS = 80,   // 17 x {c, d, sample width}: bits, or for a grouped class the bits that hold nlevels (layer2/mod.rs:183)
+    MPA12_TOTAL = 131
+};
+// time slots per packet and channel of a layer (layer1/mod.rs:193, layer2/mod.rs:383), 0 for anything else
+constexpr int mpa12_n_frames(int layer) { return layer == SYMACCEL_MPA_LAYER1 ? 12 : layer == SYMACCEL_MPA_LAYER2 ? 36 : 0; }
 
 struct ImdctPlan {
     int n;
@@ -279,6 +293,10 @@ int launch_mp3_requantize(symaccel_ctx *ctx, const int16_t *d_quant, const symac
 int launch_mpa_polyphase(symaccel_ctx *ctx, int n_frames, const float *d_in, const float *d_vvec_in,
                          const int32_t *d_vfront_in, float *d_vvec_out, int32_t *d_vfront_out, float *d_pcm, size_t n_chains,
                          size_t packets_per_chain);
+// mpa_polyphase.hip, the fused form: codes + records in, dequantised on load (d_status may be null)
+int launch_mpa12_decode(symaccel_ctx *ctx, int layer, const uint16_t *d_codes, const uint8_t *d_rec, uint8_t *d_status,
+                        const float *d_vvec_in, const int32_t *d_vfront_in, float *d_vvec_out, int32_t *d_vfront_out, float *d_pcm,
+                        size_t n_chains, size_t packets_per_chain);
 int launch_alac_predict(symaccel_ctx *ctx, int32_t *d_buf, const symaccel_alac_desc *d_desc, const int32_t *d_coeffs,
                         size_t n_blocks, size_t blocksize, const int32_t *d_pair_weight = nullptr,
                         const uint8_t *d_pair_shift = nullptr, size_t stride = 0 /* words between rows; 0 = blocksize */);

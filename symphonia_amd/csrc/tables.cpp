@@ -107,6 +107,63 @@ const unsigned short kMixed8kTail[36] = {40,  44,  48,  56,  64,  72,  84,  96, 
                                          176, 196, 216, 240, 264, 288, 316, 344, 372, 408, 444, 480,
                                          482, 484, 486, 488, 490, 492, 494, 496, 498, 524, 550, 576};
 
+// Layer I / II scale factors, ISO/IEC 11172-3 Table 3-B.1 as the standard prints it (2^(1 - i / 3) to 14 decimals), in the order of
+// layer12.rs:9-76: plain f32 literals, as the reference holds them.  Index 63 is not in the standard: the reference's 0.0.
+const float kMpa12ScaleFactors[64] = {
+    2.00000000000000f, 1.58740105196820f, 1.25992104989487f, 1.00000000000000f, 0.79370052598410f, 0.62996052494744f,
+    0.50000000000000f, 0.39685026299205f, 0.31498026247372f, 0.25000000000000f, 0.19842513149602f, 0.15749013123686f,
+    0.12500000000000f, 0.09921256574801f, 0.07874506561843f, 0.06250000000000f, 0.04960628287401f, 0.03937253280921f,
+    0.03125000000000f, 0.02480314143700f, 0.01968626640461f, 0.01562500000000f, 0.01240157071850f, 0.00984313320230f,
+    0.00781250000000f, 0.00620078535925f, 0.00492156660115f, 0.00390625000000f, 0.00310039267963f, 0.00246078330058f,
+    0.00195312500000f, 0.00155019633981f, 0.00123039165029f, 0.00097656250000f, 0.00077509816991f, 0.00061519582514f,
+    0.00048828125000f, 0.00038754908495f, 0.00030759791257f, 0.00024414062500f, 0.00019377454248f, 0.00015379895629f,
+    0.00012207031250f, 0.00009688727124f, 0.00007689947814f, 0.00006103515625f, 0.00004844363562f, 0.00003844973907f,
+    0.00003051757813f, 0.00002422181781f, 0.00001922486954f, 0.00001525878906f, 0.00001211090890f, 0.00000961243477f,
+    0.00000762939453f, 0.00000605545445f, 0.00000480621738f, 0.00000381469727f, 0.00000302772723f, 0.00000240310869f,
+    0.00000190734863f, 0.00000151386361f, 0.00000120155435f, 0.0f,
+};
+
+// Layer II quantisation classes, ISO/IEC 11172-3 Table 3-B.4 in the order of layer2/mod.rs:46-64: C and D as the standard prints
+// them, plain f32 literals as the reference holds them (the f32 nearest to the DECIMAL is what the reference multiplies with: D of the
+// two widest classes is not a power of two in f32), the bits of a sample or grouped codeword, and the number of levels.
+struct Mpa2Class {
+    float c, d;
+    unsigned char grouping, bits;
+    unsigned short nlevels;
+};
+const Mpa2Class kMpa2Classes[kMpa12Classes] = {
+    {1.33333333333f, 0.50000000000f, 1, 5, 3},      {1.60000000000f, 0.50000000000f, 1, 7, 5},
+    {1.14285714286f, 0.25000000000f, 0, 3, 7},      {1.77777777777f, 0.50000000000f, 1, 10, 9},
+    {1.06666666666f, 0.12500000000f, 0, 4, 15},     {1.03225806452f, 0.06250000000f, 0, 5, 31},
+    {1.01587301587f, 0.03125000000f, 0, 6, 63},     {1.00787401575f, 0.01562500000f, 0, 7, 127},
+    {1.00392156863f, 0.00781250000f, 0, 8, 255},    {1.00195694716f, 0.00390625000f, 0, 9, 511},
+    {1.00097751711f, 0.00195312500f, 0, 10, 1023},  {1.00048851979f, 0.00097656250f, 0, 11, 2047},
+    {1.00024420024f, 0.00048828125f, 0, 12, 4095},  {1.00012208522f, 0.00024414063f, 0, 13, 8191},
+    {1.00006103888f, 0.00012207031f, 0, 14, 16383}, {1.00003051851f, 0.00006103516f, 0, 15, 32767},
+    {1.00001525902f, 0.00003051758f, 0, 16, 65535},
+};
+
+void build_mpa12(float *tbl) {
+    // layer1/mod.rs:19-47: factor[nb] = (2^nb as f32 / (2^nb - 1) as f32) * (2^(nb - 1) as f32).recip(), nb = 2..15
+    tbl[MPA12_FACTOR] = tbl[MPA12_FACTOR + 1] = 0.0f;
+    for (int i = 2; i < 16; ++i) {
+        const int a = 1 << i, b = 1 << (i - 1);
+        const float q = (float)a / (float)(a - 1), r = 1.0f / (float)b;
+        tbl[MPA12_FACTOR + i] = q * r;
+    }
+    for (int i = 0; i < 64; ++i) tbl[MPA12_SCF + i] = kMpa12ScaleFactors[i];  // layer12.rs:9-76
+    // layer2/mod.rs:46-64 and :183 (a grouped class's samples are nlevels.next_power_of_two().trailing_zeros() bits wide)
+    for (int k = 0; k < kMpa12Classes; ++k) {
+        const Mpa2Class &q = kMpa2Classes[k];
+        unsigned width = q.bits;
+        if (q.grouping)
+            for (width = 0; (1u << width) < q.nlevels; ++width) {}
+        tbl[MPA12_CLASS + 3 * k] = q.c;
+        tbl[MPA12_CLASS + 3 * k + 1] = q.d;
+        tbl[MPA12_CLASS + 3 * k + 2] = (float)width;
+    }
+}
+
 void build(HostTables &t) {
     aac_kbd(4.0f, 1024, t.aac_kbd_long);
     aac_kbd(6.0f, 128, t.aac_kbd_short);
@@ -231,6 +288,7 @@ void build(HostTables &t) {
     for (int i = 0; i < 8207; ++i) t.mp3_pow43[i] = ::powf((float)i, 4.0f / 3.0f);
     for (int i = 0; i < kMp3Pow2abLen; ++i) t.mp3_pow2ab[i] = (float)::pow(2.0, 0.25 * (double)(kMp3Pow2abMinE + i));
     for (int i = 0; i < 256; ++i) std::memcpy(&t.vorbis_floor1_db[i], &SYM_VORBIS_FLOOR1_DB_BITS[i], 4);
+    build_mpa12(t.mpa12);
 }
 
 }  // namespace
