@@ -36,6 +36,7 @@ mod lookahead;
 mod mpa;
 pub mod mpa12;
 mod pcm;
+pub mod pcmdec;
 mod vorbis;
 
 pub use aac::{AacFrontEnd, HipAacDecoder, ParsedAac};

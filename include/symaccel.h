@@ -798,6 +798,55 @@ int symaccel_adpcm_decode_device(symaccel_ctx *ctx, const void *d_bytes, size_t 
 int symaccel_adpcm_decode(symaccel_ctx *ctx, const void *h_bytes, size_t block_pitch, size_t n_blocks, int codec, size_t channels,
                           size_t frames_per_block, void *h_pcm, int out_fmt, uint8_t *h_status);
 
+/* ------------------------------------------------------------------ PCM and G.711: packet bytes to PCM (csrc/pcm_decode.hip)
+ * symphonia-codec-pcm (lib.rs:318-411): a packet of `len` bytes is floor(len / (coded bytes * channels)) interleaved frames -- a
+ * trailing partial frame is dropped, no packet can fail (the render's Result is discarded, lib.rs:328) -- and a sample is
+ * `(read << shift).into_sample()` (lib.rs:50-84; shift = bits_per_sample - bits_per_coded_sample, :307; the shift drops high bits in
+ * the width of the sample type, the 24-bit types being read left-justified in 32 bits, :336-360), the bytes reinterpreted (F32 / F64:
+ * NaN payloads, -0.0 and denormals pass bit for bit), or alaw_to_linear / mulaw_to_linear (:154-181).  One codec per CODEC_ID_PCM_* of
+ * is_supported_pcm_codec (the line of lib.rs beside each): */
+#define SYMACCEL_PCM_S32LE 1  /* lib.rs:186 */
+#define SYMACCEL_PCM_S32BE 2  /* lib.rs:187 */
+#define SYMACCEL_PCM_S24LE 3  /* lib.rs:188 */
+#define SYMACCEL_PCM_S24BE 4  /* lib.rs:189 */
+#define SYMACCEL_PCM_S16LE 5  /* lib.rs:190 */
+#define SYMACCEL_PCM_S16BE 6  /* lib.rs:191 */
+#define SYMACCEL_PCM_S8 7     /* lib.rs:192 */
+#define SYMACCEL_PCM_U32LE 8  /* lib.rs:193 */
+#define SYMACCEL_PCM_U32BE 9  /* lib.rs:194 */
+#define SYMACCEL_PCM_U24LE 10 /* lib.rs:195 */
+#define SYMACCEL_PCM_U24BE 11 /* lib.rs:196 */
+#define SYMACCEL_PCM_U16LE 12 /* lib.rs:197 */
+#define SYMACCEL_PCM_U16BE 13 /* lib.rs:198 */
+#define SYMACCEL_PCM_U8 14    /* lib.rs:199 */
+#define SYMACCEL_PCM_F32LE 15 /* lib.rs:200 */
+#define SYMACCEL_PCM_F32BE 16 /* lib.rs:201 */
+#define SYMACCEL_PCM_F64LE 17 /* lib.rs:202 */
+#define SYMACCEL_PCM_F64BE 18 /* lib.rs:203 */
+#define SYMACCEL_PCM_ALAW 19  /* lib.rs:204 */
+#define SYMACCEL_PCM_MULAW 20 /* lib.rs:205 */
+/* Bytes of a coded sample (1 / 2 / 3 / 4 / 8) and of a sample of the reference's buffer as Rust holds it in memory (lib.rs:248-262: 1 for
+ * S8 / U8, 2 for S16 / U16 and the two log codecs, a 4-byte word for S24 (sign-extended) / U24 / S32 / U32 / F32, 8 for F64).  0 for an
+ * unknown codec.  Pure arithmetic, no context. */
+size_t symaccel_pcm_coded_bytes(int codec);
+size_t symaccel_pcm_native_bytes(int codec);
+/* n_packets packets of exactly `frames` frames each, packet k at d_bytes + k * packet_pitch (any alignment; packet_pitch >= frames *
+ * channels * coded bytes).  frames == 0 is valid and writes nothing.  out_fmt 0: d_pcm[n_packets][channels][frames], planar, in the
+ * native sample type above, aligned to its size.  out_fmt SYMACCEL_FMT_*: d_pcm[n_packets][frames][channels] interleaved samples of that
+ * format, each the reference's FromSample of the native sample (symphonia-core/src/audio/conv.rs:461-622), aligned to the sample size
+ * for the 2- and 4-byte formats.  Input and output must not overlap.  No status array: no packet can fail.
+ * SYMACCEL_ERR_UNSUPPORTED, before anything is launched, for the shapes left to the decoder below: channels 0 or above 8; a shift equal
+ * to the format's width (a coded width of 0, where Rust's `<<` overflows); any non-zero shift on the float and log codecs.
+ * SYMACCEL_ERR_INVALID_ARG for everything else that is wrong: an unknown codec or format, a shift above the width, overlap, a misaligned
+ * d_pcm, a pitch below a packet's bytes, n_packets above 2^32, frames above 2^36, packet_pitch above 2^40, or n_packets * max(packet_pitch,
+ * frames * channels * 8) above 2^62. */
+int symaccel_pcm_decode_device(symaccel_ctx *ctx, const void *d_bytes, size_t packet_pitch, size_t n_packets, int codec, size_t channels,
+                               uint32_t shift, size_t frames, void *d_pcm, int out_fmt);
+/* The same between host buffers, staged through page-locked memory, copy-in, kernel and copy-out overlapped: chunks of whole packets,
+ * or frame ranges of one packet at a time where a packet's coded bytes and output exceed a chunk (32 MiB). */
+int symaccel_pcm_decode(symaccel_ctx *ctx, const void *h_bytes, size_t packet_pitch, size_t n_packets, int codec, size_t channels,
+                        uint32_t shift, size_t frames, void *h_pcm, int out_fmt);
+
 /* ------------------------------------------------------------------ cross-stream batcher (csrc/batcher.cpp)
  * AudioDecoder::decode_ref (symphonia-core/src/codecs/audio.rs:279-297) sees one packet of one track and the registry builds
  * every decoder from (params, opts) alone (codecs/registry.rs:330-341): a decoder cannot see its siblings, so N decoders
@@ -871,7 +920,14 @@ int symaccel_adpcm_decode(symaccel_ctx *ctx, const void *h_bytes, size_t block_p
  *                              advances): the batcher reads the records in the page-locked slot when the group is launched (check_mpa12,
  *                              csrc/batcher.cpp) -- the rule is stated there and in csrc/mpa12_dequant.h and must stay in step
  *                              (tests/test_batcher_mpa12.py compares the two)
- * `units_per_chain` = frames (AAC) / granules (MP3) / blocks (Vorbis) / words (FLAC, ALAC) / bytes (ADPCM) / packets (MPA12) per chain.  Two forms:
+ *   SYMACCEL_BATCH_PCM_DECODE  symaccel_pcm_decode across streams (symphonia-codec-pcm lib.rs:318-411): a chain is ONE PACKET, units_per_chain
+ *                              = its frames, so the packets of every stream of one codec, channel count, shift and frame count share a
+ *                              launch: in = { bytes[chain][frames * channels * coded bytes] u8 }; no state; out = the native planes
+ *                              pcm[chain][channel][frames]; param = codec | channels << 8 | shift << 16.  A param symaccel_pcm_decode
+ *                              refuses (either error) is SYMACCEL_ERR_INVALID_ARG from reserve().  units_per_chain == 0 is valid for
+ *                              this kind alone: a packet of 0 frames (lib.rs:320) takes a ticket and comes back with empty planes.
+ *                              No submission can fail.
+ * `units_per_chain` = frames (AAC, PCM) / granules (MP3) / blocks (Vorbis) / words (FLAC, ALAC) / bytes (ADPCM) / packets (MPA12) per chain.  Two forms:
  *   zero-copy:  reserve() hands out a slot of page-locked staging memory (the front end writes its output straight into the DMA
  *               source), commit() says it is filled, wait() blocks until slot.out / slot.state hold the PCM and the state AFTER
  *               the batch, release() gives the slot back.  Commit a reservation before waiting for anything on the same thread.
@@ -895,6 +951,7 @@ int symaccel_adpcm_decode(symaccel_ctx *ctx, const void *h_bytes, size_t block_p
 #define SYMACCEL_BATCH_ALAC_PREDICT 8
 #define SYMACCEL_BATCH_ADPCM_DECODE 9
 #define SYMACCEL_BATCH_MPA12_DECODE 10
+#define SYMACCEL_BATCH_PCM_DECODE 11
 #define SYMACCEL_BATCH_MAX_INPUTS 6
 typedef struct symaccel_batcher symaccel_batcher;
 typedef struct symaccel_batch_slot {
@@ -961,7 +1018,8 @@ int symaccel_batcher_submit(symaccel_batcher *b, int kind, int param, size_t n_c
  * any formats and groupings share the groups and launches of their (kind, param, units_per_chain).
  * ADPCM_DECODE differs in two ways: the interleave group is ONE BLOCK's channels (channels must equal the count in param, n_chains is any
  * number of blocks; the output is [n_chains][fpb][channels] samples, S16 being lossless), and the decode kernel writes the format itself,
- * so submissions of different formats go to different launches. */
+ * so submissions of different formats go to different launches.  PCM_DECODE likewise: the interleave group is ONE PACKET's channels
+ * (channels must equal the count in param; the output is [n_chains][frames][channels] samples). */
 int symaccel_batcher_reserve_fmt(symaccel_batcher *b, int kind, int param, size_t n_chains, size_t units_per_chain, int out_fmt,
                                  int channels, symaccel_batch_slot *slot, uint64_t *ticket);
 int symaccel_batcher_submit_fmt(symaccel_batcher *b, int kind, int param, size_t n_chains, size_t units_per_chain, const void **input,
@@ -1009,6 +1067,10 @@ int symaccel_batcher_submit_alac_predict(symaccel_batcher *b, int32_t *buf_io, c
  * collect(); submit_fmt() with SYMACCEL_BATCH_ADPCM_DECODE delivers another format */
 int symaccel_batcher_submit_adpcm_decode(symaccel_batcher *b, const uint8_t *bytes, int codec, size_t channels, size_t n_blocks,
                                          size_t block_bytes, int32_t *pcm, uint64_t *ticket);
+/* symaccel_pcm_decode for n_packets packets of `frames` frames: bytes[n_packets][frames * channels * coded bytes], pcm[n_packets][channels]
+ * [frames] native samples written by collect(); submit_fmt() with SYMACCEL_BATCH_PCM_DECODE delivers another format */
+int symaccel_batcher_submit_pcm_decode(symaccel_batcher *b, const uint8_t *bytes, int codec, size_t channels, uint32_t shift,
+                                       size_t n_packets, size_t frames, void *pcm, uint64_t *ticket);
 /* wait + copy the PCM and the state after the batch into the `*_io` / `pcm` pointers given to submit + release */
 int symaccel_batcher_collect(symaccel_batcher *b, uint64_t ticket);
 /* give up a submission (seek, reset): wait until nothing of it is in flight, write nothing, release */

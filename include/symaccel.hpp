@@ -107,6 +107,13 @@ public:
                       SampleFormat out = SampleFormat::Native, std::uint8_t *h_status = nullptr) {
         check(symaccel_adpcm_decode(ctx_, h_bytes, block_pitch, n_blocks, codec, channels, frames_per_block, h_pcm, static_cast<int>(out), h_status), ctx_);
     }
+    // symphonia-codec-pcm's PcmDecoder::decode_inner (lib.rs:318-411) for n_packets packets of `frames` frames in host memory,
+    // packet_pitch bytes apart; codec: SYMACCEL_PCM_*; shift: bits_per_sample - bits_per_coded_sample (lib.rs:307).
+    // h_pcm[n_packets][channels][frames] native samples (symaccel_pcm_native_bytes each), or [n_packets][frames][channels] samples of `out`
+    void pcm_decode(const void *h_bytes, std::size_t packet_pitch, std::size_t n_packets, int codec, std::size_t channels, std::uint32_t shift, std::size_t frames,
+                    void *h_pcm, SampleFormat out = SampleFormat::Native) {
+        check(symaccel_pcm_decode(ctx_, h_bytes, packet_pitch, n_packets, codec, channels, shift, frames, h_pcm, static_cast<int>(out)), ctx_);
+    }
     // Layer1::decode / Layer2::decode behind the bit reader (layer1/mod.rs:142-194, layer2/mod.rs:320-384) for n_chains x
     // packets_per_chain channel-packets in host memory: h_codes[chain][packet][32][n_frames] u16, h_rec[chain][packet][record bytes],
     // state and PCM as mp3::synthesis takes them; h_status[chain][packet] (may be null): 1 = a record out of range, decoded as silence
@@ -583,6 +590,13 @@ struct has_packet_errors : std::false_type {};
 template <class C>
 struct has_packet_errors<C, std::void_t<decltype(std::declval<const C &>().packet_error(std::size_t{}))>> : std::true_type {};
 
+// A codec whose slot shape depends on the packets of the batch (PCM: the frames of its longest packet) is shown the batch before the slot
+// is reserved: `prepare(batch)`.
+template <class C, class = void>
+struct has_prepare : std::false_type {};
+template <class C>
+struct has_prepare<C, std::void_t<decltype(&C::prepare)>> : std::true_type {};
+
 struct FinalizeResult {  // codecs/audio.rs:230-236
     std::optional<bool> verify_ok;
 };
@@ -758,6 +772,7 @@ private:
     void submit(const std::vector<Packet> &batch) {
         if constexpr (Codec::kBatchKind != 0) {
             symaccel_batch_slot slot;
+            if constexpr (has_prepare<Codec>::value) codec_.prepare(batch);
             reserve(batch.size(), &slot, &next_ticket_);
             next_live_ = true;
             try {
@@ -1907,6 +1922,122 @@ private:
     std::vector<std::int32_t> tmp_;
 };
 
+// PCM and G.711 (symphonia-codec-pcm): the twenty codecs of PcmDecoder.  Like ADPCM there is NO CPU side: the packet's bytes go up as
+// they are and csrc/pcm_decode.hip does the de-interleave, byte order, shift, log expansion and conversion.  Nothing is carried from
+// packet to packet (lib.rs:415-417) and no packet can fail (lib.rs:328: the render's Result is discarded).
+//
+// A packet is floor(len / (coded bytes * channels)) frames (lib.rs:320), so the packets of a look-ahead batch may differ in length.  A
+// batch is ONE call (one batcher submission): every packet is a chain of `units` frames, `units` being the frames of the batch's longest
+// packet; a shorter packet is followed by zero bytes, decodes them as well, and publishes its own frame count -- streams cut their packets
+// to one size, so only the last packet of a stream pays for it, and with the batcher (SYMACCEL_BATCH_PCM_DECODE) the batches of every
+// stream of one codec, channel count, shift and frame count share launches.  A batch of empty packets is a submission of 0 frames.
+//
+// The native planes are the reference's buffer sample type as Rust holds it (symaccel_pcm_native_bytes: 1, 2, 4 or 8 bytes; i24 / u24 in a
+// 32-bit word), so Sample is a byte: `planes[c]` points at `frames * native_bytes()` bytes, to be read as variant()'s type.
+struct Pcm {
+    using Sample = std::uint8_t;
+    struct Params {  // AudioCodecParameters (codecs/audio.rs:300-400): what PcmDecoder::try_new reads
+        int codec = SYMACCEL_PCM_S16LE;  // SYMACCEL_PCM_*; anything else is a codec the reference's decoder does not take either
+        std::optional<std::uint32_t> sample_rate;
+        std::optional<std::size_t> channels;
+        std::optional<std::uint32_t> bits_per_sample, bits_per_coded_sample;
+        std::optional<std::uint64_t> max_frames_per_packet;  // (the reference pre-allocates with it; nothing here depends on it)
+    };
+    struct Packet {
+        std::uint64_t ts = 0;
+        std::vector<std::uint8_t> data;
+    };
+    // The checks of PcmDecoder::try_new in their order with their error kinds (lib.rs:220-303; the C++ Error has no DecodeError kind:
+    // Kind::IoError carrying the status SYMACCEL_ERR_DECODE is how this header spells it, as for ADPCM), then Error{Unsupported} for the
+    // shapes the device decoder leaves to the decoder below (more than 8 channels; a coded width of 0)
+    explicit Pcm(const Params &p) : codec_(p.codec), coded_(symaccel_pcm_coded_bytes(p.codec)), native_bytes_(symaccel_pcm_native_bytes(p.codec)) {
+        auto unsupported = [](const char *m) { return Error(Error::Kind::Unsupported, SYMACCEL_ERR_UNSUPPORTED, m); };
+        auto decode_error = [](const char *m) { return Error(Error::Kind::IoError, SYMACCEL_ERR_DECODE, m); };
+        if (coded_ == 0) throw unsupported("pcm: invalid codec");                                   // lib.rs:222-224
+        if (!p.sample_rate) throw unsupported("pcm: sample rate is required");                      // lib.rs:226-229
+        if (!p.channels) throw unsupported("pcm: channels or channel_layout is required");          // lib.rs:239-241
+        if (*p.channels < 1) throw unsupported("pcm: number of channels cannot be 0");              // lib.rs:233-235
+        nch_ = *p.channels;
+        const bool implicit = codec_ >= SYMACCEL_PCM_F32LE;  // the float and log codecs (lib.rs:292-303)
+        const std::uint32_t width = coded_ == 8 ? 64 : (implicit ? (coded_ == 4 ? 32 : 16) : 8 * (std::uint32_t)coded_);  // lib.rs:248-262
+        if (p.bits_per_coded_sample && *p.bits_per_coded_sample > width) throw decode_error("pcm: bits per coded sample greater-than sample format");  // :266-270
+        if (p.bits_per_sample) {
+            if (*p.bits_per_sample > width) throw decode_error("pcm: bits per sample is greater-than sample format");  // :274-277
+            if (p.bits_per_coded_sample && *p.bits_per_coded_sample > *p.bits_per_sample)
+                throw decode_error("pcm: bits per coded sample greater-than bits per sample");  // :280-284
+        }
+        const std::uint32_t decoded_width = p.bits_per_sample.value_or(width), coded_width = p.bits_per_coded_sample.value_or(decoded_width);  // :287-288
+        if (implicit) {
+            if (decoded_width != width) throw decode_error("pcm: unexpected bits per sample");        // :295-297
+            if (coded_width != width) throw decode_error("pcm: unexpected bits per coded sample");    // :298-300
+        }
+        shift_ = decoded_width - coded_width;  // :307
+        if (nch_ > 8 || (!implicit && shift_ == width)) throw unsupported("pcm: a shape the device decoder refuses");
+    }
+    static constexpr int kBatchKind = SYMACCEL_BATCH_PCM_DECODE;
+    static constexpr bool kDirect = false;
+    static constexpr bool kBlockInterleave = true;  // (a format leaves the kernel as [packet][frame][channel])
+    struct BatchView {};
+    void attach(Batcher &) {}
+    void set_output_format(SampleFormat f) { native_ = f == SampleFormat::Native; }
+    int batch_param() const { return codec_ | (int)(nch_ << 8) | (int)(shift_ << 16); }
+    std::size_t batch_chains(std::size_t k) const { return k; }
+    std::size_t batch_units(std::size_t) const { return next_units_; }
+    std::size_t native_bytes() const { return native_bytes_; }
+    std::uint32_t shift() const { return shift_; }
+    std::size_t frames_of(const Packet &p) const { return p.data.size() / (coded_ * nch_); }  // lib.rs:320
+    // the batch about to be submitted: its slot holds `units` frames per packet
+    void prepare(const std::vector<Packet> &batch) {
+        next_units_ = 0;
+        for (const Packet &p : batch) next_units_ = std::max(next_units_, frames_of(p));
+    }
+    void fill_slot(const std::vector<Packet> &batch, const symaccel_batch_slot &slot) {
+        next_frames_.assign(batch.size(), 0);
+        place(batch, static_cast<std::uint8_t *>(slot.input[0]), next_units_, next_frames_);
+    }
+    void take_state(const symaccel_batch_slot &) {
+        frames_.swap(next_frames_);
+        units_ = next_units_;
+    }
+    static std::uint64_t id(const Packet &p) { return p.ts; }
+    std::size_t channels() const { return nch_; }
+    bool device_output_is_final() const { return true; }
+    std::size_t packet_frames(std::size_t i) const { return frames_[i]; }
+    // native: BYTES in front of packet i's channel c in [packet][channel][units]; a format: the samples in front of the packet, all channels
+    std::size_t plane_offset(std::size_t c, std::size_t i, std::size_t) const {
+        return native_ ? (i * nch_ + c) * units_ * native_bytes_ : i * units_ * nch_;
+    }
+    void reset_state() {}
+    void decode_batch(Context &ctx, const std::vector<Packet> &batch, std::vector<std::uint8_t> &pcm) {
+        prepare(batch);
+        units_ = next_units_;
+        frames_.assign(batch.size(), 0);
+        rows_.resize(batch.size() * units_ * coded_ * nch_);
+        place(batch, rows_.data(), units_, frames_);
+        pcm.assign(batch.size() * nch_ * units_ * native_bytes_, 0);
+        if (batch.empty() || units_ == 0) return;
+        ctx.pcm_decode(rows_.data(), units_ * coded_ * nch_, batch.size(), codec_, nch_, shift_, units_, pcm.data(), SampleFormat::Native);
+    }
+
+private:
+    // every packet's whole frames into its row of `units` frames, zero bytes behind them
+    void place(const std::vector<Packet> &batch, std::uint8_t *rows, std::size_t units, std::vector<std::size_t> &frames) const {
+        const std::size_t fb = coded_ * nch_, pitch = units * fb;
+        for (std::size_t i = 0; i < batch.size(); ++i) {
+            frames[i] = frames_of(batch[i]);
+            std::copy_n(batch[i].data.data(), frames[i] * fb, rows + i * pitch);
+            std::fill(rows + i * pitch + frames[i] * fb, rows + (i + 1) * pitch, 0);
+        }
+    }
+    int codec_;
+    std::size_t coded_, native_bytes_, nch_ = 0;
+    std::uint32_t shift_ = 0;
+    std::size_t units_ = 0, next_units_ = 0;  // frames every packet of the current / the submitted batch occupies
+    bool native_ = true;
+    std::vector<std::size_t> frames_, next_frames_;
+    std::vector<std::uint8_t> rows_;
+};
+
 // CodecRegistry (symphonia-core/src/codecs/registry.rs:220-341).  The reference's registry maps a codec id to a factory that is handed
 // (params, options) and NOTHING ELSE -- `RegisterableAudioDecoder::try_registry_new` (registry.rs:34-44) -- so a decoder it builds cannot
 // be told about its siblings: the factories here find the process-wide batcher themselves (`Batcher::shared()`), exactly as the Rust shim's
@@ -1961,6 +2092,8 @@ inline void register_enabled_codecs(CodecRegistry &registry) {
 }
 // ... and ADPCM, entered by a call of its own (the shim's `adpcm::register`): the list above is the one the shim's `register()` has
 inline void register_adpcm(CodecRegistry &registry) { registry.register_audio_decoder<Adpcm>(); }
+// ... and PCM / G.711 (the twenty CODEC_ID_PCM_* of symphonia-codec-pcm), likewise
+inline void register_pcm(CodecRegistry &registry) { registry.register_audio_decoder<Pcm>(); }
 // ... and MPEG Layer I / II (CODEC_ID_MP1 / CODEC_ID_MP2), likewise
 inline void register_mpa12(CodecRegistry &registry) { registry.register_audio_decoder<Mpa12>(); }
 

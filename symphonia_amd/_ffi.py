@@ -31,6 +31,12 @@ FMT_U8, FMT_S8, FMT_U16, FMT_S16, FMT_U24, FMT_S24, FMT_U32, FMT_S32, FMT_F32 = 
 # SYMACCEL_ADPCM_*: the codecs of symaccel_adpcm_decode
 ADPCM_MS, ADPCM_IMA_WAV, ADPCM_IMA_QT = 1, 2, 3
 
+# SYMACCEL_PCM_*: the codecs of symaccel_pcm_decode, in the order of include/symaccel.h
+PCM_CODEC_NAMES = ("s32le", "s32be", "s24le", "s24be", "s16le", "s16be", "s8", "u32le", "u32be", "u24le", "u24be", "u16le", "u16be", "u8",
+                   "f32le", "f32be", "f64le", "f64be", "alaw", "mulaw")
+(PCM_S32LE, PCM_S32BE, PCM_S24LE, PCM_S24BE, PCM_S16LE, PCM_S16BE, PCM_S8, PCM_U32LE, PCM_U32BE, PCM_U24LE, PCM_U24BE, PCM_U16LE, PCM_U16BE,
+ PCM_U8, PCM_F32LE, PCM_F32BE, PCM_F64LE, PCM_F64BE, PCM_ALAW, PCM_MULAW) = range(1, 21)
+
 # every symbol include/symaccel.h declares (tests/test_abi.py checks the built library exports all)
 ABI_SYMBOLS = [
     "symaccel_abi_version", "symaccel_strerror", "symaccel_last_error", "symaccel_ctx_create",
@@ -66,6 +72,8 @@ ABI_SYMBOLS = [
     "symaccel_batcher_reserve_fmt", "symaccel_batcher_submit_fmt",
     "symaccel_adpcm_block_bytes", "symaccel_adpcm_decode_device", "symaccel_adpcm_decode",
     "symaccel_batcher_submit_adpcm_decode",
+    "symaccel_pcm_coded_bytes", "symaccel_pcm_native_bytes", "symaccel_pcm_decode_device", "symaccel_pcm_decode",
+    "symaccel_batcher_submit_pcm_decode",
     "symaccel_mpa12_record_bytes", "symaccel_mpa12_decode_device", "symaccel_mpa12_decode_pp_device", "symaccel_mpa12_decode",
 ]
 
@@ -172,6 +180,7 @@ class Library:
         d.symaccel_batcher_submit_flac_restore.argtypes = [_vp, _vp, _vp, _vp, _vp, _u32, _sz, _sz, C.POINTER(C.c_uint64)]
         d.symaccel_batcher_submit_alac_predict.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, C.POINTER(C.c_uint64)]
         d.symaccel_batcher_submit_adpcm_decode.argtypes = [_vp, _vp, _i, _sz, _sz, _sz, _vp, C.POINTER(C.c_uint64)]
+        d.symaccel_batcher_submit_pcm_decode.argtypes = [_vp, _vp, _i, _sz, C.c_uint, _sz, _sz, _vp, C.POINTER(C.c_uint64)]
         d.symaccel_aac_decode_pipelined.argtypes = [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _i, _vp, _i, _vp, _sz, _vp, _vp, _sz, _sz, _sz]
         d.symaccel_mp3_stereo_device.argtypes = [_vp, _vp, _sz, _vp, _vp, _i, _sz]
         d.symaccel_mp3_requantize_stereo_device.argtypes = [_vp, _vp, _vp, _sz, _vp, _vp, _i, _vp, _sz]
@@ -247,6 +256,12 @@ class Library:
         d.symaccel_adpcm_block_bytes.restype = _sz
         d.symaccel_adpcm_decode_device.argtypes = [_vp, _vp, _sz, _sz, _i, _sz, _sz, _vp, _i, _vp]
         d.symaccel_adpcm_decode.argtypes = [_vp, _vp, _sz, _sz, _i, _sz, _sz, _vp, _i, _vp]
+        d.symaccel_pcm_coded_bytes.argtypes = [_i]
+        d.symaccel_pcm_coded_bytes.restype = _sz
+        d.symaccel_pcm_native_bytes.argtypes = [_i]
+        d.symaccel_pcm_native_bytes.restype = _sz
+        d.symaccel_pcm_decode_device.argtypes = [_vp, _vp, _sz, _sz, _i, _sz, C.c_uint, _sz, _vp, _i]
+        d.symaccel_pcm_decode.argtypes = [_vp, _vp, _sz, _sz, _i, _sz, C.c_uint, _sz, _vp, _i]
         d.symaccel_mpa12_record_bytes.argtypes = [_i]
         d.symaccel_mpa12_record_bytes.restype = _sz
         d.symaccel_mpa12_decode_device.argtypes = [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz]

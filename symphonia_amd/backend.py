@@ -831,6 +831,61 @@ def adpcm_decode_device(ctx, src, block_pitch, n_blocks, codec, channels, frames
               status if isinstance(status, int) or status is None else _ptr(status))
 
 
+# ---- PCM and G.711: packet bytes to PCM (symaccel_pcm_decode) ---------------------------------------------------------------------
+PCM_CODECS = {name: i + 1 for i, name in enumerate(_ffi.PCM_CODEC_NAMES)}
+from ._ffi import (PCM_S32LE, PCM_S32BE, PCM_S24LE, PCM_S24BE, PCM_S16LE, PCM_S16BE, PCM_S8, PCM_U32LE, PCM_U32BE, PCM_U24LE, PCM_U24BE,  # noqa: E402, F401
+                   PCM_U16LE, PCM_U16BE, PCM_U8, PCM_F32LE, PCM_F32BE, PCM_F64LE, PCM_F64BE, PCM_ALAW, PCM_MULAW)
+_PCM_NATIVE_DTYPES = {"s32": np.int32, "s24": np.int32, "s16": np.int16, "s8": np.int8, "u32": np.uint32, "u24": np.uint32, "u16": np.uint16,
+                      "u8": np.uint8, "f32": np.float32, "f64": np.float64, "ala": np.int16, "mul": np.int16}
+
+
+def pcm_codec(codec):
+    """A SYMACCEL_PCM_* value from a value or a name ("s16le", "s24be", "u8", "f64le", "alaw", "mulaw", ...)."""
+    return PCM_CODECS[codec.lower()] if isinstance(codec, str) else int(codec)
+
+
+def pcm_native_dtype(codec):
+    """The numpy type of a native sample of a codec (the 24-bit codecs: a 32-bit word)."""
+    return np.dtype(_PCM_NATIVE_DTYPES[_ffi.PCM_CODEC_NAMES[pcm_codec(codec) - 1][:3]])
+
+
+def pcm_coded_bytes(codec, lib=None):
+    """symaccel_pcm_coded_bytes: bytes of a coded sample; 0 for an unknown codec."""
+    lib = lib if lib is not None else _ffi.default_library()
+    return int(lib.dll.symaccel_pcm_coded_bytes(pcm_codec(codec)))
+
+
+def pcm_native_bytes(codec, lib=None):
+    """symaccel_pcm_native_bytes: bytes of a sample of the reference's buffer; 0 for an unknown codec."""
+    lib = lib if lib is not None else _ffi.default_library()
+    return int(lib.dll.symaccel_pcm_native_bytes(pcm_codec(codec)))
+
+
+def pcm_decode(ctx, packets, codec, channels, frames=None, shift=0, out_fmt=0):
+    """symaccel_pcm_decode: packets[n_packets, packet_pitch] uint8 in host memory (a row holds one packet of `frames` frames; by default
+    as many whole frames as a row holds).  out_fmt 0: the native planes [n_packets, channels, frames] in the codec's native type;
+    a format (value or name): uint8[n_packets, frames * channels * sample_bytes], interleaved."""
+    b = np.ascontiguousarray(packets, dtype=np.uint8)
+    if b.ndim != 2:
+        raise ValueError("packets must be a [n_packets, packet_pitch] array of uint8")
+    codec, channels, out_fmt = pcm_codec(codec), int(channels), sample_format(out_fmt)
+    if frames is None:
+        frames = b.shape[1] // max(channels * pcm_coded_bytes(codec, ctx.lib), 1)
+    frames = int(frames)
+    if out_fmt == 0:
+        pcm = np.zeros((b.shape[0], max(channels, 0), max(frames, 0)), pcm_native_dtype(codec) if 1 <= codec <= 20 else np.uint8)
+    else:
+        pcm = np.zeros((b.shape[0], max(frames * channels, 0) * sample_bytes(out_fmt, ctx.lib)), np.uint8)
+    ctx._call(ctx.lib.dll.symaccel_pcm_decode, _ptr(b), b.shape[1], b.shape[0], codec, channels, int(shift), frames, _ptr(pcm), out_fmt)
+    return pcm
+
+
+def pcm_decode_device(ctx, src, packet_pitch, n_packets, codec, channels, shift, frames, dst, out_fmt=0):
+    """symaccel_pcm_decode_device on device memory (torch tensors, or raw addresses).  Asynchronous on the context's stream."""
+    ctx._call(ctx.lib.dll.symaccel_pcm_decode_device, src if isinstance(src, int) or src is None else _ptr(src), int(packet_pitch), int(n_packets),
+              pcm_codec(codec), int(channels), int(shift), int(frames), dst if isinstance(dst, int) or dst is None else _ptr(dst), sample_format(out_fmt))
+
+
 ALAC_DESC_DTYPE = np.dtype([("mode", np.uint8), ("lpc_order", np.uint8), ("shift", np.uint8), ("bps", np.uint8)])
 
 
@@ -987,6 +1042,7 @@ BATCH_AAC_SYNTH, BATCH_MP3_SYNTH, BATCH_MP3_DECODE, BATCH_VORBIS_SYNTH, BATCH_AA
 BATCH_VORBIS_DECODE, BATCH_FLAC_RESTORE, BATCH_ALAC_PREDICT = 6, 7, 8
 BATCH_ADPCM_DECODE = 9
 BATCH_MPA12_DECODE = 10
+BATCH_PCM_DECODE = 11
 BATCH_MAX_INPUTS = 6
 
 
@@ -1152,6 +1208,22 @@ class Batcher:
             return self.submit(BATCH_ADPCM_DECODE, adpcm_codec(codec) | int(channels) << 8, [blocks], [], pcm, out_format=out_format, channels=channels)
         self._check(self.dll.symaccel_batcher_submit_adpcm_decode(self.handle, blocks.ctypes.data, adpcm_codec(codec), int(channels), int(blocks.shape[0]),
                                                                   int(blocks.shape[1]), pcm.ctypes.data, C.byref(t)))
+        return int(t.value)
+
+    def submit_pcm_decode(self, packets, codec, channels, pcm, shift=0, out_format=0):
+        """symaccel_batcher_submit_pcm_decode: packets uint8[n_packets, frames * channels * coded bytes], pcm [n_packets, channels, frames]
+        native samples written by collect(); with out_format (a FMT_* value or name) `pcm` receives [n_packets][frames][channels] samples
+        of that format instead (symaccel_batcher_submit_fmt)"""
+        assert packets.flags["C_CONTIGUOUS"] and pcm.flags["C_CONTIGUOUS"] and packets.dtype == np.uint8 and packets.ndim == 2
+        codec, channels = pcm_codec(codec), int(channels)
+        frames = packets.shape[1] // max(channels * pcm_coded_bytes(codec, self.ctx.lib), 1)
+        assert frames * channels * pcm_coded_bytes(codec, self.ctx.lib) == packets.shape[1]
+        t = C.c_uint64()
+        if out_format:
+            return self.submit(BATCH_PCM_DECODE, codec | channels << 8 | int(shift) << 16, [packets], [], pcm, out_format=out_format, channels=channels,
+                               units=frames)
+        self._check(self.dll.symaccel_batcher_submit_pcm_decode(self.handle, packets.ctypes.data, codec, channels, int(shift), int(packets.shape[0]),
+                                                                frames, pcm.ctypes.data, C.byref(t)))
         return int(t.value)
 
     def reserve(self, kind, param, n_chains, units, out_format=0, channels=0):

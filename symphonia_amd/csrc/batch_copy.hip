@@ -253,3 +253,6 @@ int launch_batch_copy(symaccel_ctx *ctx, hipStream_t stream, const BatchCopyDesc
 
 // The ADPCM decode kernels and their launcher (a file of their own, compiled as part of this translation unit)
 #include "adpcm.hip"
+
+// The PCM / G.711 decode kernels and their launcher (likewise)
+#include "pcm_decode.hip"

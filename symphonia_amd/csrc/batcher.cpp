@@ -155,6 +155,17 @@ bool plane_sizes(int kind, int param, size_t units, PlaneSizes *ps) {
         ps->out = units * 32 * nf * 4;
         return true;
     }
+    case SYMACCEL_BATCH_PCM_DECODE: {  // symaccel_pcm_decode: bytes | no state | pcm; a chain is a PACKET, units = its frames
+        // param = codec | channels << 8 | shift << 16 (| out_fmt << 24 inside the batcher, as for ADPCM_DECODE)
+        const PcmDecParam pp = pcmdec_param(param);
+        if (param < 0 || (param >> 28) || units > 0x3fffffffu) return false;
+        if (pcm_decode_shape_status(kPcmDecMaxPitch, 1, pp.codec, (size_t)pp.nch, (unsigned)pp.shift, units, pp.fmt) != SYMACCEL_OK) return false;
+        const PcmCodec pc = pcm_codec(pp.codec);
+        ps->n_in = 1;
+        ps->in[0] = units * (size_t)pp.nch * pc.coded;
+        ps->out = units * (size_t)pp.nch * (pp.fmt ? symaccel_sample_bytes(pp.fmt) : pc.native);
+        return true;
+    }
     default: return false;
     }
 }
@@ -714,6 +725,10 @@ int launch_chunk(symaccel_ctx *ctx, Group *g, const Chunk &ch) {
         return launch_adpcm_decode(ctx, ctx->stream, in[0], g->units, ch.nc, ap.codec, (unsigned)ap.nch,
                                    (unsigned)adpcm_frames_of_bytes(ap.codec, (size_t)ap.nch, g->units), ch.out, ap.fmt, nullptr);
     }
+    case SYMACCEL_BATCH_PCM_DECODE: {  // symphonia-codec-pcm lib.rs:318-411 (the packets of the chunk, back to back)
+        const PcmDecParam pp = pcmdec_param(g->param);
+        return launch_pcm_decode(ctx, ctx->stream, in[0], g->ps.in[0], ch.nc, pp.codec, (unsigned)pp.nch, (unsigned)pp.shift, g->units, ch.out, pp.fmt);
+    }
     case SYMACCEL_BATCH_MPA12_DECODE:  // layer1/mod.rs:142-194, layer2/mod.rs:320-384 (no status plane: check_mpa12 judged the records)
         return launch_mpa12_decode(ctx, g->param, (const uint16_t *)in[0], (const uint8_t *)in[1], nullptr, (const float *)si[0], (const int32_t *)si[1],
                                    (float *)so[0], (int32_t *)so[1], (float *)ch.out, ch.nc, g->units);
@@ -1124,12 +1139,20 @@ int symaccel_batcher_reserve(symaccel_batcher *b, int kind, int param, size_t n_
 
 int symaccel_batcher_reserve_fmt(symaccel_batcher *b, int kind, int param, size_t n_chains, size_t units_per_chain, int out_fmt, int channels,
                                  symaccel_batch_slot *slot, uint64_t *ticket) {
-    if (!b || !slot || !ticket || n_chains == 0 || units_per_chain == 0 || n_chains > 0x7fffffffu) return SYMACCEL_ERR_INVALID_ARG;
+    if (!b || !slot || !ticket || n_chains == 0 || n_chains > 0x7fffffffu) return SYMACCEL_ERR_INVALID_ARG;
+    // (a PCM packet of 0 frames is a packet like any other -- lib.rs:320: floor(len / frame bytes) -- with empty planes: it takes a ticket,
+    // rides in the group of its shape and comes back with 0 bytes)
+    if (units_per_chain == 0 && kind != SYMACCEL_BATCH_PCM_DECODE) return SYMACCEL_ERR_INVALID_ARG;
     if (kind == SYMACCEL_BATCH_ADPCM_DECODE) {
         // the interleave group is one block's channels, and the decode kernel itself writes the format: the format joins the group key,
         // and from here on the submission is an ordinary one whose output plane holds [chain][frame][channel] samples of out_fmt
         if (param < 0 || (param >> 16) || (out_fmt != 0 && (symaccel_sample_bytes(out_fmt) == 0 || channels != adpcm_param(param).nch))) return SYMACCEL_ERR_INVALID_ARG;
         param |= out_fmt << 16;
+        out_fmt = channels = 0;
+    }
+    if (kind == SYMACCEL_BATCH_PCM_DECODE) {  // likewise: the interleave group is one packet's channels, the kernel writes the format
+        if (param < 0 || (param >> 24) || (out_fmt != 0 && (symaccel_sample_bytes(out_fmt) == 0 || channels != pcmdec_param(param).nch))) return SYMACCEL_ERR_INVALID_ARG;
+        param |= out_fmt << 24;
         out_fmt = channels = 0;
     }
     if (out_fmt != 0 && (symaccel_sample_bytes(out_fmt) == 0 || channels < 1 || channels > 8 || n_chains % (size_t)channels != 0)) return SYMACCEL_ERR_INVALID_ARG;
@@ -1339,6 +1362,7 @@ int symaccel_batcher_submit_fmt(symaccel_batcher *b, int kind, int param, size_t
     if (kind == SYMACCEL_BATCH_AAC_DECODE) return SYMACCEL_ERR_INVALID_ARG;  // (symaccel_batcher_submit_aac_decode writes the blob)
     PlaneSizes ps;
     if (kind == SYMACCEL_BATCH_ADPCM_DECODE && (param < 0 || (param >> 16))) return SYMACCEL_ERR_INVALID_ARG;  // (the format travels in out_fmt)
+    if (kind == SYMACCEL_BATCH_PCM_DECODE && (param < 0 || (param >> 24))) return SYMACCEL_ERR_INVALID_ARG;    // (likewise)
     if (!plane_sizes(kind, kind == SYMACCEL_BATCH_AAC_SYNTH ? 0 : param, units_per_chain, &ps)) return SYMACCEL_ERR_INVALID_ARG;
     for (int i = 0; i < ps.n_in; ++i)
         if (!in[i] && !(kind == SYMACCEL_BATCH_MP3_DECODE && i == 3 && n_chains == 1)) return SYMACCEL_ERR_INVALID_ARG;
@@ -1530,6 +1554,14 @@ int symaccel_batcher_submit_adpcm_decode(symaccel_batcher *b, const uint8_t *byt
     const void *in[kMaxIn] = {bytes, nullptr, nullptr, nullptr, nullptr, nullptr};
     void *st[3] = {nullptr, nullptr, nullptr};
     return symaccel_batcher_submit(b, SYMACCEL_BATCH_ADPCM_DECODE, codec | (int)(channels << 8), n_blocks, block_bytes, in, st, pcm, ticket);
+}
+
+int symaccel_batcher_submit_pcm_decode(symaccel_batcher *b, const uint8_t *bytes, int codec, size_t channels, uint32_t shift, size_t n_packets,
+                                       size_t frames, void *pcm, uint64_t *ticket) {
+    if (codec < 0 || codec > 255 || channels > 255 || shift > 255) return SYMACCEL_ERR_INVALID_ARG;
+    const void *in[kMaxIn] = {bytes, nullptr, nullptr, nullptr, nullptr, nullptr};
+    void *st[3] = {nullptr, nullptr, nullptr};
+    return symaccel_batcher_submit(b, SYMACCEL_BATCH_PCM_DECODE, codec | (int)(channels << 8) | (int)(shift << 16), n_packets, frames, in, st, pcm, ticket);
 }
 
 int symaccel_batcher_submit_alac_predict(symaccel_batcher *b, int32_t *buf_io, const symaccel_alac_desc *desc, const int32_t *coeffs,

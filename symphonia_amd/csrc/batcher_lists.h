@@ -50,6 +50,10 @@ struct AdpcmParam {  // ADPCM_DECODE: codec | channels << 8 | out_fmt << 16 (the
     int codec, nch, fmt;
 };
 inline AdpcmParam adpcm_param(int param) { return {param & 255, (param >> 8) & 255, (param >> 16) & 255}; }
+struct PcmDecParam {  // PCM_DECODE: codec | channels << 8 | shift << 16 | out_fmt << 24 (the format joins inside the batcher: reserve_fmt)
+    int codec, nch, shift, fmt;
+};
+inline PcmDecParam pcmdec_param(int param) { return {param & 255, (param >> 8) & 255, (param >> 16) & 255, (param >> 24) & 15}; }
 struct PairParam {  // FLAC_RESTORE: 0, or 0x100 | out_shift; ALAC_PREDICT: 0 or 0x100 -- the fused stereo forms
     bool pairs;
     uint32_t shift;

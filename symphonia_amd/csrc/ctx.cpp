@@ -1197,6 +1197,28 @@ int symaccel_adpcm_decode_device(symaccel_ctx *ctx, const void *d_bytes, size_t 
     return launch_adpcm_decode(ctx, ctx->stream, d_bytes, block_pitch, n_blocks, codec, (unsigned)channels, (unsigned)frames_per_block, d_pcm, out_fmt, d_status);
 }
 
+// ---- PCM / G.711 ------------------------------------------------------------------------------
+
+size_t symaccel_pcm_coded_bytes(int codec) { return pcm_codec(codec).coded; }
+size_t symaccel_pcm_native_bytes(int codec) { return pcm_codec(codec).native; }
+
+int symaccel_pcm_decode_device(symaccel_ctx *ctx, const void *d_bytes, size_t packet_pitch, size_t n_packets, int codec, size_t channels,
+                               uint32_t shift, size_t frames, void *d_pcm, int out_fmt) {
+    if (!ctx) return SYMACCEL_ERR_INVALID_ARG;
+    SYM_TRY(pcm_decode_shape_status(packet_pitch, n_packets, codec, channels, shift, frames, out_fmt));
+    const PcmCodec pc = pcm_codec(codec);
+    const size_t b = out_fmt == 0 ? pc.native : symaccel_sample_bytes(out_fmt);
+    const uintptr_t s0 = (uintptr_t)d_bytes, t0 = (uintptr_t)d_pcm;
+    if ((b == 2 || b == 4 || b == 8) && t0 % b != 0) return SYMACCEL_ERR_INVALID_ARG;
+    if (n_packets == 0 || frames == 0) return SYMACCEL_OK;
+    if (!d_bytes || !d_pcm) return SYMACCEL_ERR_INVALID_ARG;
+    const size_t src_bytes = (n_packets - 1) * packet_pitch + frames * channels * pc.coded, dst_bytes = n_packets * frames * channels * b;
+    if (s0 < t0 + dst_bytes && t0 < s0 + src_bytes) return SYMACCEL_ERR_INVALID_ARG;  // overlapping buffers
+    DeviceGuard dev(ctx);
+    if (!dev.ok()) return dev.status();
+    return launch_pcm_decode(ctx, ctx->stream, d_bytes, packet_pitch, n_packets, codec, (unsigned)channels, shift, frames, d_pcm, out_fmt);
+}
+
 // ---- per-record status arrays --------------------------------------------------------------
 
 int symaccel_flac_block_status_device(symaccel_ctx *ctx, const symaccel_flac_desc *d_desc, size_t n_blocks, size_t blocksize,

@@ -110,6 +110,79 @@ __device__ __forceinline__ uint32_t pcm_from_i32(uint32_t bits) {
     }
 }
 
+// ---- the eight further source types: the buffers symphonia-codec-pcm decodes into (pcm_decode.hip) -----------------------------------
+//
+// A native sample arrives as Rust holds it: an i8 / i16 sign-extended, an i24 sign-extended and in range (sample.rs:272-276: every i24
+// the decoder makes is `i24::from`, clamped), a u8 / u16 / u24 / u32 zero-extended, an f64 as its 64 bits.
+//
+// Every integer conversion of conv.rs:461-592 is the i32 one (conv.rs:521-532) of the sample left-justified in 32 bits, for an unsigned
+// source with the top bit flipped (u32 -> i32 is wrapping_sub(2^31), conv.rs:589):
+//   * to an integer both sides keep the top bytes of that word, after the same flip of the top bit (i8_to_u8, i16_to_u16, i24_to_u32,
+//     wrapping_sub(0x80..)); `clamped()` changes no value that is in range;
+//   * to f32 the narrow sources divide the sample by 2^(width-1) and the unsigned ones then subtract 1.0 (conv.rs:471, 491, 511, 546,
+//     561, 576): an integer of at most 24 bits is exact in f32, so is its quotient by a power of two, and (s - 2^(w-1)) / 2^(w-1) has at
+//     most 24 significant bits, so the subtraction is exact too -- the value is that of the left-justified word over 2^31, which is what
+//     conv.rs:531 rounds (nothing to round here).  u32 (conv.rs:591) is computed in f64, exactly, and rounded once, as conv.rs:531 is.
+template <int DST>
+__device__ __forceinline__ uint32_t pcm_from_i8(uint32_t s) { return pcm_from_i32<DST>(s << 24); }  // conv.rs:461-471
+template <int DST>
+__device__ __forceinline__ uint32_t pcm_from_i16(uint32_t s) { return pcm_from_i32<DST>(s << 16); }  // conv.rs:481-491
+template <int DST>
+__device__ __forceinline__ uint32_t pcm_from_i24(uint32_t s) { return pcm_from_i32<DST>(s << 8); }  // conv.rs:501-511
+template <int DST>
+__device__ __forceinline__ uint32_t pcm_from_u8(uint32_t s) { return pcm_from_i32<DST>((s << 24) ^ 0x80000000u); }  // conv.rs:536-546
+template <int DST>
+__device__ __forceinline__ uint32_t pcm_from_u16(uint32_t s) { return pcm_from_i32<DST>((s << 16) ^ 0x80000000u); }  // conv.rs:551-561
+template <int DST>
+__device__ __forceinline__ uint32_t pcm_from_u24(uint32_t s) { return pcm_from_i32<DST>((s << 8) ^ 0x80000000u); }  // conv.rs:566-576
+template <int DST>
+__device__ __forceinline__ uint32_t pcm_from_u32(uint32_t s) { return pcm_from_i32<DST>(s ^ 0x80000000u); }  // conv.rs:581-591
+
+// util.rs:270-275 (a NaN fails both comparisons and passes)
+__device__ __forceinline__ double pcm_clamp_f64(double v) {
+    double c = v;
+    c = c > 1.0 ? 1.0 : c;
+    c = c < -1.0 ? -1.0 : c;
+    return c;
+}
+
+// Rust's `x as uN` for x in [0, 2^N] or NaN: truncation, saturation at 2^N - 1, NaN -> 0
+__device__ __forceinline__ uint32_t pcm_f64_as_unsigned(double x, double two_n, uint32_t max) {
+    if (!(x > 0.0)) return 0u;
+    return x >= two_n ? max : (uint32_t)x;
+}
+
+// Rust's `x as iN` for |x| <= 2^(N-1) or NaN
+__device__ __forceinline__ int32_t pcm_f64_as_signed(double x, double two_n1, int32_t max) {
+    if (x != x) return 0;
+    return x >= two_n1 ? max : (int32_t)x;
+}
+
+// conv.rs:611-621.  The arithmetic is the reference's, in f64, one rounding per operation.
+template <int DST>
+__device__ __forceinline__ uint32_t pcm_from_f64(uint64_t bits) {
+    if constexpr (DST == SYMACCEL_FMT_F32) {
+        // conv.rs:621, `s as f32`: round to nearest even.  A NaN keeps its sign and the top 22 bits of its payload and becomes quiet -- what
+        // the conversion instructions of the reference's targets and of this device make of it, written out so that it holds everywhere
+        if ((bits & 0x7fffffffffffffffull) > 0x7ff0000000000000ull)
+            return (uint32_t)(bits >> 32 & 0x80000000u) | 0x7fc00000u | (uint32_t)(bits >> 29 & 0x3fffffu);
+        return __float_as_uint((float)__builtin_bit_cast(double, bits));
+    } else {
+        const double c = pcm_clamp_f64(__builtin_bit_cast(double, bits));
+        if constexpr (DST == SYMACCEL_FMT_U8) return pcm_f64_as_unsigned((c + 1.0) * 128.0, 256.0, 0xffu);  // conv.rs:611
+        else if constexpr (DST == SYMACCEL_FMT_U16) return pcm_f64_as_unsigned((c + 1.0) * 32768.0, 65536.0, 0xffffu);  // conv.rs:612
+        else if constexpr (DST == SYMACCEL_FMT_U24) return pcm_f64_as_unsigned((c + 1.0) * 8388608.0, 16777216.0, 0xffffffu);  // conv.rs:613 (u24::from clamps)
+        else if constexpr (DST == SYMACCEL_FMT_U32) return pcm_f64_as_unsigned((c + 1.0) * 2147483648.0, 4294967296.0, 0xffffffffu);  // conv.rs:614
+        else if constexpr (DST == SYMACCEL_FMT_S8) return (uint32_t)pcm_f64_as_signed(c * 128.0, 128.0, 0x7f) & 0xffu;  // conv.rs:616
+        else if constexpr (DST == SYMACCEL_FMT_S16) return (uint32_t)pcm_f64_as_signed(c * 32768.0, 32768.0, 0x7fff) & 0xffffu;  // conv.rs:617
+        else if constexpr (DST == SYMACCEL_FMT_S24) return (uint32_t)pcm_f64_as_signed(c * 8388608.0, 8388608.0, 0x7fffff) & 0xffffffu;  // conv.rs:618
+        else {
+            static_assert(DST == SYMACCEL_FMT_S32, "unknown destination format");
+            return (uint32_t)pcm_f64_as_signed(c * 2147483648.0, 2147483648.0, 0x7fffffff);  // conv.rs:619
+        }
+    }
+}
+
 // SRC: SYMACCEL_FMT_F32 or SYMACCEL_FMT_S32
 template <int SRC, int DST>
 __device__ __forceinline__ uint32_t pcm_convert_sample(uint32_t bits) {

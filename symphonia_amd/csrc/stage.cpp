@@ -94,6 +94,8 @@ struct Pipe {
         return SYMACCEL_OK;
     }
     // everything queued so far, on all three streams
+    // run_chunks() returns drained; a caller that goes on to queue more work says so first
+    void rearm() { queued = true; }
     int drain() {
         SYM_GPU(ctx, hipStreamSynchronize(s_in));
         SYM_GPU(ctx, hipStreamSynchronize(ctx->stream));
@@ -176,11 +178,13 @@ int copy_rows(symaccel_ctx *ctx, void *dst, size_t dpitch, const void *src, size
     return SYMACCEL_OK;
 }
 
+constexpr size_t kChunkBytes = (size_t)32 << 20;
+
 size_t pick_chunk(size_t units_per_chain, size_t bytes_per_unit_all_chains, size_t requested, size_t min_units) {
     if (requested > 0) return std::min(requested, units_per_chain);
     // ~32 MiB of input per chunk: large enough to fill the GPU (hundreds of wavefront segments) and to amortise the
     // per-copy latency, small enough that the first kernel starts early and the last copy-out finishes soon after the last kernel
-    size_t c = ((size_t)32 << 20) / std::max<size_t>(1, bytes_per_unit_all_chains);
+    size_t c = kChunkBytes / std::max<size_t>(1, bytes_per_unit_all_chains);
     c = std::max(c, min_units);
     return std::min(c, units_per_chain);
 }
@@ -510,6 +514,61 @@ int symaccel_adpcm_decode(symaccel_ctx *ctx, const void *h_bytes, size_t block_p
             if (h_status) SYM_GPU(ctx, hipMemcpyAsync(h_status + b0, d_st[b], nb, hipMemcpyDeviceToHost, pp.s_out));
             return SYMACCEL_OK;
         });
+}
+
+// symaccel_pcm_decode_device between host buffers.  Packets whose coded bytes and output fit a chunk go in chunks of whole packets, at
+// a device pitch that is a multiple of 16 bytes; larger ones go one packet at a time in chunks of frame ranges, whose native planes
+// come back row by row into the caller's planes.
+int symaccel_pcm_decode(symaccel_ctx *ctx, const void *h_bytes, size_t packet_pitch, size_t n_packets, int codec, size_t channels,
+                        uint32_t shift, size_t frames, void *h_pcm, int out_fmt) {
+    if (!ctx) return SYMACCEL_ERR_INVALID_ARG;
+    SYM_TRY(pcm_decode_shape_status(packet_pitch, n_packets, codec, channels, shift, frames, out_fmt));
+    if (n_packets == 0 || frames == 0) return SYMACCEL_OK;
+    if (!h_bytes || !h_pcm) return SYMACCEL_ERR_INVALID_ARG;
+    const PcmCodec pc = pcm_codec(codec);
+    const size_t sb = out_fmt == 0 ? pc.native : symaccel_sample_bytes(out_fmt);
+    const size_t frame_in = channels * pc.coded, frame_out = channels * sb, bytes = frames * frame_in, out_bytes = frames * frame_out;
+    const uintptr_t s0 = (uintptr_t)h_bytes, t0 = (uintptr_t)h_pcm;
+    if (s0 < t0 + n_packets * out_bytes && t0 < s0 + (n_packets - 1) * packet_pitch + bytes) return SYMACCEL_ERR_INVALID_ARG;  // overlapping buffers
+    const uint8_t *src = static_cast<const uint8_t *>(h_bytes);
+    uint8_t *dst = static_cast<uint8_t *>(h_pcm);
+    Pipe pp(ctx);
+    SYM_TRY(pp.init());
+    uint8_t *d_in[2], *d_out[2];
+    if (bytes + out_bytes <= kChunkBytes) {  // whole packets
+        const size_t d_pitch = (bytes + 15) & ~(size_t)15, cp = pick_chunk(n_packets, d_pitch + out_bytes, 0, 1);
+        pp.alloc2(d_in, cp * d_pitch);
+        pp.alloc2(d_out, cp * out_bytes);
+        SYM_TRY(pp.commit());
+        return run_chunks(pp, n_packets, cp, false, nullptr,
+            [&](int b, size_t p0, size_t np) { return copy_rows(ctx, d_in[b], d_pitch, src + p0 * packet_pitch, packet_pitch, bytes, np, hipMemcpyHostToDevice, pp.s_in); },
+            [&](size_t, int b, size_t np) { return launch_pcm_decode(ctx, ctx->stream, d_in[b], d_pitch, np, codec, (unsigned)channels, shift, frames, d_out[b], out_fmt); },
+            [&](int b, size_t p0, size_t np) -> int {
+                SYM_GPU(ctx, hipMemcpyAsync(dst + p0 * out_bytes, d_out[b], np * out_bytes, hipMemcpyDeviceToHost, pp.s_out));
+                return SYMACCEL_OK;
+            });
+    }
+    // frame ranges of one packet
+    const size_t cf = pick_chunk(frames, frame_in + frame_out, 0, 16);
+    pp.alloc2(d_in, cf * frame_in);
+    pp.alloc2(d_out, cf * frame_out);
+    SYM_TRY(pp.commit());
+    for (size_t p = 0; p < n_packets; ++p) {
+        const uint8_t *ps = src + p * packet_pitch;
+        uint8_t *pd = dst + p * out_bytes;
+        pp.rearm();
+        SYM_TRY(run_chunks(pp, frames, cf, false, nullptr,
+            [&](int b, size_t f0, size_t nf) -> int {
+                SYM_GPU(ctx, hipMemcpyAsync(d_in[b], ps + f0 * frame_in, nf * frame_in, hipMemcpyHostToDevice, pp.s_in));
+                return SYMACCEL_OK;
+            },
+            [&](size_t, int b, size_t nf) { return launch_pcm_decode(ctx, ctx->stream, d_in[b], nf * frame_in, 1, codec, (unsigned)channels, shift, nf, d_out[b], out_fmt); },
+            [&](int b, size_t f0, size_t nf) {
+                if (out_fmt == 0) return copy_rows(ctx, pd + f0 * sb, frames * sb, d_out[b], nf * sb, nf * sb, channels, hipMemcpyDeviceToHost, pp.s_out);
+                return copy_rows(ctx, pd + f0 * frame_out, nf * frame_out, d_out[b], nf * frame_out, nf * frame_out, 1, hipMemcpyDeviceToHost, pp.s_out);
+            }));
+    }
+    return SYMACCEL_OK;
 }
 
 // symaccel_mpa12_decode_pp_device between host buffers: chunks of whole packets; the synthesis state ping-pongs on the device.

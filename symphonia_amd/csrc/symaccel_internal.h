@@ -390,6 +390,66 @@ inline int adpcm_shape_status(size_t block_pitch, size_t n_blocks, int codec, si
 }
 int launch_adpcm_decode(symaccel_ctx *ctx, hipStream_t stream, const void *d_bytes, size_t block_pitch, size_t n_blocks, int codec, unsigned channels,
                         unsigned frames_per_block, void *d_pcm, int out_fmt, uint8_t *d_status);
+// pcm_decode.hip: what a SYMACCEL_PCM_* codec is (symphonia-codec-pcm lib.rs:248-262, 328-388)
+enum PcmKind { PCM_KIND_SIGNED, PCM_KIND_UNSIGNED, PCM_KIND_F32, PCM_KIND_F64, PCM_KIND_ALAW, PCM_KIND_MULAW };
+struct PcmCodec {
+    unsigned coded;   // bytes of a coded sample: 1, 2, 3, 4, 8; 0 = an unknown codec
+    unsigned native;  // bytes of a sample of the reference's buffer as Rust holds it: 1, 2, 4 (i24 / u24 are a u32 / i32 word), 8
+    unsigned width;   // bits of the buffer's sample format (sample_format_width)
+    PcmKind kind;
+    bool big_endian;
+};
+inline PcmCodec pcm_codec(int codec) {
+    switch (codec) {
+    case SYMACCEL_PCM_S32LE: return {4, 4, 32, PCM_KIND_SIGNED, false};
+    case SYMACCEL_PCM_S32BE: return {4, 4, 32, PCM_KIND_SIGNED, true};
+    case SYMACCEL_PCM_S24LE: return {3, 4, 24, PCM_KIND_SIGNED, false};
+    case SYMACCEL_PCM_S24BE: return {3, 4, 24, PCM_KIND_SIGNED, true};
+    case SYMACCEL_PCM_S16LE: return {2, 2, 16, PCM_KIND_SIGNED, false};
+    case SYMACCEL_PCM_S16BE: return {2, 2, 16, PCM_KIND_SIGNED, true};
+    case SYMACCEL_PCM_S8: return {1, 1, 8, PCM_KIND_SIGNED, false};
+    case SYMACCEL_PCM_U32LE: return {4, 4, 32, PCM_KIND_UNSIGNED, false};
+    case SYMACCEL_PCM_U32BE: return {4, 4, 32, PCM_KIND_UNSIGNED, true};
+    case SYMACCEL_PCM_U24LE: return {3, 4, 24, PCM_KIND_UNSIGNED, false};
+    case SYMACCEL_PCM_U24BE: return {3, 4, 24, PCM_KIND_UNSIGNED, true};
+    case SYMACCEL_PCM_U16LE: return {2, 2, 16, PCM_KIND_UNSIGNED, false};
+    case SYMACCEL_PCM_U16BE: return {2, 2, 16, PCM_KIND_UNSIGNED, true};
+    case SYMACCEL_PCM_U8: return {1, 1, 8, PCM_KIND_UNSIGNED, false};
+    case SYMACCEL_PCM_F32LE: return {4, 4, 32, PCM_KIND_F32, false};
+    case SYMACCEL_PCM_F32BE: return {4, 4, 32, PCM_KIND_F32, true};
+    case SYMACCEL_PCM_F64LE: return {8, 8, 64, PCM_KIND_F64, false};
+    case SYMACCEL_PCM_F64BE: return {8, 8, 64, PCM_KIND_F64, true};
+    case SYMACCEL_PCM_ALAW: return {1, 2, 16, PCM_KIND_ALAW, false};
+    case SYMACCEL_PCM_MULAW: return {1, 2, 16, PCM_KIND_MULAW, false};
+    default: return {0, 0, 0, PCM_KIND_SIGNED, false};
+    }
+}
+// The extents symaccel_pcm_decode(_device) accept: they keep every byte offset below 2^62
+constexpr size_t kPcmDecMaxPackets = (size_t)1 << 32, kPcmDecMaxFrames = (size_t)1 << 36, kPcmDecMaxPitch = (size_t)1 << 40, kPcmDecMaxBytes = (size_t)1 << 62;
+// what symaccel_pcm_decode(_device) refuse, pointers aside: SYMACCEL_OK, or the error.  UNSUPPORTED is what the reference's decoder takes
+// and this one leaves to it (lib.rs:231-241 any channel count; :307 a coded width of 0, where `<<` by the whole width overflows; a
+// shift on the codecs whose widths :292-303 pin, which try_new never produces)
+inline int pcm_decode_shape_status(size_t packet_pitch, size_t n_packets, int codec, size_t channels, unsigned shift, size_t frames, int out_fmt) {
+    const PcmCodec pc = pcm_codec(codec);
+    if (pc.coded == 0 || (out_fmt != 0 && symaccel_sample_bytes(out_fmt) == 0)) return SYMACCEL_ERR_INVALID_ARG;
+    if (channels < 1 || channels > kPcmMaxChannels) return SYMACCEL_ERR_UNSUPPORTED;
+    const bool integer = pc.kind == PCM_KIND_SIGNED || pc.kind == PCM_KIND_UNSIGNED;
+    if (integer ? shift == pc.width : shift != 0) return SYMACCEL_ERR_UNSUPPORTED;
+    if (shift > pc.width) return SYMACCEL_ERR_INVALID_ARG;
+    if (n_packets > kPcmDecMaxPackets || frames > kPcmDecMaxFrames || packet_pitch > kPcmDecMaxPitch) return SYMACCEL_ERR_INVALID_ARG;
+    if (packet_pitch < frames * channels * pc.coded) return SYMACCEL_ERR_INVALID_ARG;
+    const size_t per_packet = std::max<size_t>(packet_pitch, frames * channels * 8);
+    if (n_packets != 0 && per_packet > kPcmDecMaxBytes / n_packets) return SYMACCEL_ERR_INVALID_ARG;
+    return SYMACCEL_OK;
+}
+// Frames of a tile of pcm_decode.hip: a multiple of 16, with the tile's coded bytes and its output (and the up to 31 bytes of alignment
+// slack of each of its up to 8 output runs) inside kPcmTileBytes
+constexpr unsigned pcm_decode_tile_frames(unsigned channels, unsigned coded_bytes, unsigned out_bytes) {
+    return ((kPcmTileBytes - 256u) / (channels * (coded_bytes > out_bytes ? coded_bytes : out_bytes))) & ~15u;
+}
+// (the caller has checked the shape, the pointers' alignment and the sizes: symaccel_pcm_decode_device)
+int launch_pcm_decode(symaccel_ctx *ctx, hipStream_t stream, const void *d_bytes, size_t packet_pitch, size_t n_packets, int codec, unsigned channels,
+                      unsigned shift, size_t frames, void *d_pcm, int out_fmt);
 int launch_probe_copy(symaccel_ctx *ctx, const void *d_src, void *d_dst, size_t bytes, unsigned frames_per_wavefront, unsigned flags);
 int launch_flac_decorrelate(symaccel_ctx *ctx, const uint8_t *d_mode, int32_t *d_ch0, int32_t *d_ch1,
                             size_t n_pairs, size_t blocksize, uint32_t out_shift);

@@ -2105,6 +2105,9 @@ class Interp:
             return _struct.unpack('<d', _struct.pack('<Q', v.v))[0]
         if name in ('from_le_bytes', 'from_be_bytes', 'from_ne_bytes'):
             bs = bytes(x.v for x in seq_list(args[0]))
+            if ty in ('f32', 'f64'):  # the bytes reinterpreted: NaN payloads, -0.0 and denormals pass
+                bs = bs[::-1] if name == 'from_be_bytes' else bs
+                return np.frombuffer(bs, '<f4')[0] if ty == 'f32' else _struct.unpack('<d', bs)[0]
             return Int(int.from_bytes(bs, 'big' if name == 'from_be_bytes' else 'little', signed=ty[0] == 'i'), ty)
         # f64::sqrt(x), u32::min(a, b), ... : the method form
         if args:
