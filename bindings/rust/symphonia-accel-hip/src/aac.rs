@@ -8,14 +8,13 @@ use std::sync::{Arc, Mutex};
 use symphonia_codec_aac::{AacDecoder, CodedChannel, JointStereo, SynthBackend, JOINT_STEREO_INTENSITY, JOINT_STEREO_MID_SIDE};
 use symphonia_core::audio::{Audio, AudioBuffer, AudioMut, AudioSpec, GenericAudioBufferRef};
 use symphonia_core::codecs::audio::well_known::CODEC_ID_AAC;
-use symphonia_core::codecs::audio::{AudioCodecParameters, AudioDecoder, AudioDecoderOptions, FinalizeResult};
-use symphonia_core::codecs::registry::{RegisterableAudioDecoder, SupportedAudioCodec};
-use symphonia_core::codecs::CodecInfo;
+use symphonia_core::codecs::audio::{AudioCodecParameters, AudioDecoder, AudioDecoderOptions};
 use symphonia_core::errors::{decode_error, unsupported_error, Result};
 use symphonia_core::packet::PacketRef;
 use symphonia_core::support_audio_codec;
 
 use crate::ctx::{check, Context, Pinned, Pool};
+use crate::decoder::DecoderBatch;
 use crate::ffi;
 use crate::lookahead::{BatchCodec, Lookahead};
 
@@ -469,24 +468,22 @@ impl AacBatch {
     }
 }
 
-/// AAC-LC decoder with the same observable behaviour as `symphonia_codec_aac::AacDecoder`.
-pub struct HipAacDecoder {
-    params: AudioCodecParameters,
-    batch: AacBatch,
-    la: Lookahead<ParsedAac>,
+impl DecoderBatch for AacBatch {
+    fn buffer(&self) -> GenericAudioBufferRef<'_> {
+        self.buf.as_generic_audio_buffer_ref()
+    }
 }
 
+crate::hip_decoder!(
+    HipAacDecoder,
+    AacBatch,
+    ParsedAac,
+    &[support_audio_codec!(CODEC_ID_AAC, "aac", "Advanced Audio Coding (MI355X synthesis)")],
+    "AAC-LC decoder with the same observable behaviour as `symphonia_codec_aac::AacDecoder`."
+);
+crate::hip_decoder!(@new HipAacDecoder, crate::frontends::aac_front_end, Box<dyn AacFrontEnd>);
+
 impl HipAacDecoder {
-    pub fn try_new(params: &AudioCodecParameters, opts: &AudioDecoderOptions, front: Box<dyn AacFrontEnd>, max_batch: usize) -> Result<Self> {
-        Self::try_new_with_pool(params, opts, front, max_batch, None)
-    }
-
-    /// The same decoder submitting to the process-wide cross-stream batcher (`Pool::shared()`, `SYMACCEL_BATCH_AAC_DECODE`): with
-    /// many streams open, joint stereo, TNS and synthesis of all of them run in one launch (csrc/batcher.cpp).
-    pub fn try_new_pooled(params: &AudioCodecParameters, opts: &AudioDecoderOptions, front: Box<dyn AacFrontEnd>, max_batch: usize) -> Result<Self> {
-        Self::try_new_with_pool(params, opts, front, max_batch, Some(Pool::shared()?))
-    }
-
     pub fn try_new_with_pool(
         _params: &AudioCodecParameters,
         _opts: &AudioDecoderOptions,
@@ -521,55 +518,5 @@ impl HipAacDecoder {
             },
             la: Lookahead::new(max_batch),
         })
-    }
-}
-
-impl AudioDecoder for HipAacDecoder {
-    fn reset(&mut self) {
-        self.la.reset_with(&mut self.batch); // (a batch still with the cross-stream batcher is given up first)
-        self.batch.reset_state();
-    }
-
-    fn codec_info(&self) -> &CodecInfo {
-        &Self::supported_codecs()[0].info
-    }
-
-    fn codec_params(&self) -> &AudioCodecParameters {
-        &self.params
-    }
-
-    fn decode_ref(&mut self, packet: &PacketRef<'_>) -> Result<GenericAudioBufferRef<'_>> {
-        // (Lookahead::decode clears the buffer on every error path: codecs/audio.rs:278)
-        self.la.decode(&mut self.batch, packet)?;
-        Ok(self.batch.buf.as_generic_audio_buffer_ref())
-    }
-
-    fn finalize(&mut self) -> FinalizeResult {
-        Default::default()
-    }
-
-    fn last_decoded(&self) -> GenericAudioBufferRef<'_> {
-        self.batch.buf.as_generic_audio_buffer_ref()
-    }
-}
-
-impl RegisterableAudioDecoder for HipAacDecoder {
-    fn try_registry_new(params: &AudioCodecParameters, opts: &AudioDecoderOptions) -> Result<Box<dyn AudioDecoder>> {
-        // The registry builds every decoder from (params, opts) alone (codecs/registry.rs:330-341): the decoders it builds find each
-        // other in the process-wide `Pool` -- their look-ahead batches go to the device in common launches (csrc/batcher.cpp).  Only
-        // when the pool cannot be created does a decoder batch on its own.
-        // No front end, no device, no memory: the decoder that was registered below this one takes the track.
-        let built = crate::frontends::aac_front_end(params, opts).and_then(|front| match Pool::shared() {
-            Ok(pool) => HipAacDecoder::try_new_with_pool(params, opts, front, crate::DEFAULT_LOOKAHEAD, Some(pool)),
-            Err(_) => HipAacDecoder::try_new(params, opts, front, crate::DEFAULT_LOOKAHEAD),
-        });
-        match built {
-            Ok(decoder) => Ok(Box::new(decoder)),
-            Err(e) => crate::fallback::make(params, opts, e),
-        }
-    }
-
-    fn supported_codecs() -> &'static [SupportedAudioCodec] {
-        &[support_audio_codec!(CODEC_ID_AAC, "aac", "Advanced Audio Coding (MI355X synthesis)")]
     }
 }

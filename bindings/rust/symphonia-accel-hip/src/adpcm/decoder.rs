@@ -2,23 +2,22 @@
 //! its blocks and makes, per packet, the checks the reference's readers make (a packet shorter than its blocks: the I/O error of
 //! `BufReader`; an MS block predictor above 6: `Unsupported`; an IMA WAV step index above 88: `DecodeError` -- whichever the reference
 //! meets first), so a packet fails alone and only blocks the kernel accepts reach the device; `transform` / `submit` hand the blocks of a
-//! whole look-ahead batch to `symaccel_adpcm_decode` or to the cross-stream batcher (`SYMACCEL_BATCH_ADPCM_DECODE`: a chain is a block);
-//! `publish` copies a packet's blocks from `[block][channel][frame]` into the planes.  `register` enters the decoder at
-//! `Tier::Preferred`.  Shapes the device decoder refuses go to the decoder below (`fallback.rs`).  No seam patch and no `frontends.rs`
+//! whole look-ahead batch to `symaccel_adpcm_decode` or to the cross-stream batcher (`SYMACCEL_BATCH_ADPCM_DECODE`: a chain is a block;
+//! its slots through `SlotCycle`, ctx.rs); `publish` copies a packet's blocks from `[block][channel][frame]` into the planes.
+//! `register` enters the decoder at `Tier::Preferred`.  Shapes the device decoder refuses go to the decoder below (`fallback.rs`).  No seam patch and no `frontends.rs`
 //! entry are needed: there is no host front end.
 use std::sync::Arc;
 
 use symphonia_core::audio::{Audio, AudioBuffer, AudioMut, AudioSpec, Channels, GenericAudioBufferRef};
 use symphonia_core::codecs::audio::well_known::{CODEC_ID_ADPCM_IMA_QT, CODEC_ID_ADPCM_IMA_WAV, CODEC_ID_ADPCM_MS};
-use symphonia_core::codecs::audio::{AudioCodecParameters, AudioDecoder, AudioDecoderOptions, FinalizeResult};
-use symphonia_core::codecs::registry::{CodecRegistry, RegisterableAudioDecoder, SupportedAudioCodec};
-use symphonia_core::codecs::CodecInfo;
+use symphonia_core::codecs::audio::{AudioCodecParameters, AudioDecoderOptions};
+use symphonia_core::codecs::registry::CodecRegistry;
 use symphonia_core::errors::{decode_error, unsupported_error, Error, Result};
 use symphonia_core::packet::PacketRef;
 use symphonia_core::support_audio_codec;
 
 use crate::adpcm::AdpcmCodec;
-use crate::ctx::{check, BatchSlot, Context, Pool};
+use crate::ctx::{check, Context, Pool, SlotCycle};
 use crate::decoder::DecoderBatch;
 use crate::ffi;
 use crate::lookahead::{BatchCodec, Lookahead};
@@ -93,19 +92,40 @@ pub struct AdpcmBatch {
     bytes: Vec<u8>,     // the blocks of the current batch, back to back
     pcm: Vec<i32>,      // [block][channel][frame]
     status: Vec<u8>,
+    // the cross-stream batcher through the slot cycle of ctx.rs: the PCM of a batch that came through it is read in its page-locked slot
+    slots: SlotCycle<AdpcmIndex>,
+    buf: AudioBuffer<i32>,
+}
+
+/// Where `publish` finds a packet in its batch.
+pub struct AdpcmIndex {
     first: Vec<usize>,  // first block of each packet of the batch
     lens: Vec<usize>,   // blocks of each packet
-    pool: Option<Arc<Pool>>,
-    cur: Option<BatchSlot>,
-    next: Option<BatchSlot>,
-    next_first: Vec<usize>,
-    next_lens: Vec<usize>,
-    buf: AudioBuffer<i32>,
+    total: usize,
 }
 
 impl AdpcmBatch {
     fn param(&self) -> i32 {
         self.shape.codec.raw() | ((self.shape.channels as i32) << 8)
+    }
+
+    fn index_of(batch: &[ParsedAdpcm]) -> AdpcmIndex {
+        let mut first = Vec::with_capacity(batch.len());
+        let mut total = 0;
+        for p in batch {
+            first.push(total);
+            total += p.blocks;
+        }
+        AdpcmIndex { first, lens: batch.iter().map(|p| p.blocks).collect(), total }
+    }
+
+    /// The blocks of a batch back to back: what `symaccel_adpcm_decode` and the batcher's slot both take.
+    fn place(rows: &mut [u8], batch: &[ParsedAdpcm]) {
+        let mut at = 0;
+        for p in batch {
+            rows[at..at + p.data.len()].copy_from_slice(&p.data);
+            at += p.data.len();
+        }
     }
 }
 
@@ -157,20 +177,13 @@ impl BatchCodec for AdpcmBatch {
     }
 
     fn transform(&mut self, batch: &[ParsedAdpcm]) -> Result<()> {
-        if let (Some(pool), Some(old)) = (self.pool.clone(), self.cur.take()) {
-            pool.release(old);
-        }
+        let index = Self::index_of(batch);
+        let total = index.total;
+        self.slots.start_direct(index);
         let (nch, fpb) = (self.shape.channels, self.shape.frames_per_block);
         self.bytes.clear();
-        self.first.clear();
-        self.lens.clear();
-        let mut total = 0;
-        for p in batch {
-            self.first.push(total);
-            self.lens.push(p.blocks);
-            self.bytes.extend_from_slice(&p.data);
-            total += p.blocks;
-        }
+        self.bytes.resize(total * self.shape.block_bytes, 0u8);
+        Self::place(&mut self.bytes, batch);
         self.pcm.clear();
         self.pcm.resize(total * nch * fpb, 0i32);
         self.status.clear();
@@ -188,13 +201,11 @@ impl BatchCodec for AdpcmBatch {
 
     fn publish(&mut self, i: usize) {
         let (nch, fpb) = (self.shape.channels, self.shape.frames_per_block);
-        let (first, blocks) = (self.first[i], self.lens[i]);
+        let ix = self.slots.index();
+        let (first, blocks) = (ix.first[i], ix.lens[i]);
         self.buf.clear();
         self.buf.render_uninit(Some(blocks * fpb));
-        let pcm: &[i32] = match &self.cur {
-            Some(slot) => slot.out::<i32>(),
-            None => self.pcm.as_slice(),
-        };
+        let pcm: &[i32] = self.slots.out::<i32>().unwrap_or(self.pcm.as_slice());
         for c in 0..nch {
             if let Some(plane) = self.buf.plane_mut(c) {
                 for j in 0..blocks {
@@ -213,76 +224,31 @@ impl BatchCodec for AdpcmBatch {
     }
 
     fn pooled(&self) -> bool {
-        self.pool.is_some()
+        self.slots.pooled()
     }
 
     fn submit(&mut self, batch: &[ParsedAdpcm]) -> Result<()> {
-        let Some(pool) = self.pool.clone() else {
-            return unsupported_error("adpcm: no batcher");
-        };
-        let total: usize = batch.iter().map(|p| p.blocks).sum();
-        if total == 0 || self.next.is_some() {
-            return unsupported_error("adpcm: one batch of at least one block at a time");
+        let index = Self::index_of(batch);
+        if index.total == 0 {
+            return unsupported_error("adpcm: a batch of at least one block");
         }
-        let mut slot = pool.reserve(ffi::SYMACCEL_BATCH_ADPCM_DECODE as i32, self.param(), total, self.shape.block_bytes)?;
-        self.next_first.clear();
-        self.next_lens.clear();
-        {
-            let rows = slot.input::<u8>(0);
-            let mut at = 0;
-            let mut block = 0;
-            for p in batch {
-                rows[at..at + p.data.len()].copy_from_slice(&p.data);
-                at += p.data.len();
-                self.next_first.push(block);
-                self.next_lens.push(p.blocks);
-                block += p.blocks;
-            }
-        }
-        if let Err(e) = pool.commit(&mut slot) {
-            pool.release(slot);
-            return Err(e);
-        }
-        self.next = Some(slot);
-        Ok(())
+        let (param, total) = (self.param(), index.total);
+        self.slots.submit(ffi::SYMACCEL_BATCH_ADPCM_DECODE as i32, param, total, self.shape.block_bytes, index, |slot| {
+            Self::place(slot.input::<u8>(0), batch);
+            Ok(())
+        })
     }
 
     fn collect(&mut self) -> Result<()> {
-        let (Some(pool), Some(mut slot)) = (self.pool.clone(), self.next.take()) else {
-            return unsupported_error("adpcm: nothing was submitted");
-        };
-        if let Err(e) = pool.wait(&mut slot) {
-            pool.release(slot);
-            return Err(e);
-        }
-        if let Some(old) = self.cur.take() {
-            pool.release(old);
-        }
-        self.cur = Some(slot);
-        std::mem::swap(&mut self.first, &mut self.next_first);
-        std::mem::swap(&mut self.lens, &mut self.next_lens);
-        Ok(())
+        self.slots.collect(|_| {})
     }
 
     fn hint(&mut self) {
-        if let Some(pool) = &self.pool {
-            pool.hint();
-        }
+        self.slots.hint();
     }
 
     fn abandon(&mut self) {
-        if let (Some(pool), Some(slot)) = (self.pool.clone(), self.next.take()) {
-            pool.release(slot);
-        }
-    }
-}
-
-impl Drop for AdpcmBatch {
-    fn drop(&mut self) {
-        BatchCodec::abandon(self);
-        if let (Some(pool), Some(slot)) = (self.pool.clone(), self.cur.take()) {
-            pool.release(slot);
-        }
+        self.slots.abandon();
     }
 }
 
@@ -292,23 +258,20 @@ impl DecoderBatch for AdpcmBatch {
     }
 }
 
-/// ADPCM decoder with the same observable behaviour as `symphonia_codec_adpcm::AdpcmDecoder`.
-pub struct HipAdpcmDecoder {
-    params: AudioCodecParameters,
-    batch: AdpcmBatch,
-    la: Lookahead<ParsedAdpcm>,
-}
+crate::hip_decoder!(
+    HipAdpcmDecoder,
+    AdpcmBatch,
+    ParsedAdpcm,
+    &[
+        support_audio_codec!(CODEC_ID_ADPCM_MS, "adpcm_ms", "Microsoft ADPCM (MI355X)"),
+        support_audio_codec!(CODEC_ID_ADPCM_IMA_WAV, "adpcm_ima_wav", "ADPCM IMA WAV (MI355X)"),
+        support_audio_codec!(CODEC_ID_ADPCM_IMA_QT, "adpcm_ima_qt", "ADPCM IMA QT (MI355X)"),
+    ],
+    "ADPCM decoder with the same observable behaviour as `symphonia_codec_adpcm::AdpcmDecoder`."
+);
+crate::hip_decoder!(@new HipAdpcmDecoder);
 
 impl HipAdpcmDecoder {
-    pub fn try_new(params: &AudioCodecParameters, opts: &AudioDecoderOptions, max_batch: usize) -> Result<Self> {
-        Self::try_new_with_pool(params, opts, max_batch, None)
-    }
-
-    /// The same decoder submitting to the process-wide cross-stream batcher (`Pool::shared()`).
-    pub fn try_new_pooled(params: &AudioCodecParameters, opts: &AudioDecoderOptions, max_batch: usize) -> Result<Self> {
-        Self::try_new_with_pool(params, opts, max_batch, Some(Pool::shared()?))
-    }
-
     pub fn try_new_with_pool(params: &AudioCodecParameters, opts: &AudioDecoderOptions, max_batch: usize, pool: Option<Arc<Pool>>) -> Result<Self> {
         let shape = adpcm_shape(params, opts)?;
         let buf = AudioBuffer::new(AudioSpec::new(shape.rate, shape.layout.clone()), shape.max_frames);
@@ -320,71 +283,11 @@ impl HipAdpcmDecoder {
                 bytes: Vec::new(),
                 pcm: Vec::new(),
                 status: Vec::new(),
-                first: Vec::new(),
-                lens: Vec::new(),
-                pool,
-                cur: None,
-                next: None,
-                next_first: Vec::new(),
-                next_lens: Vec::new(),
+                slots: SlotCycle::new(pool, AdpcmBatch::index_of(&[])),
                 buf,
             },
             la: Lookahead::new(max_batch.max(1)),
         })
-    }
-}
-
-impl AudioDecoder for HipAdpcmDecoder {
-    /// Nothing is carried between packets (lib.rs:217-219): only what was computed ahead is dropped.
-    fn reset(&mut self) {
-        self.la.reset_with(&mut self.batch);
-        BatchCodec::reset_state(&mut self.batch);
-    }
-
-    fn codec_info(&self) -> &CodecInfo {
-        // the codec that is in use (lib.rs:176-183)
-        &Self::supported_codecs().iter().find(|desc| desc.id == self.params.codec).expect("codec registered in supported_codecs").info
-    }
-
-    fn codec_params(&self) -> &AudioCodecParameters {
-        &self.params
-    }
-
-    fn decode_ref(&mut self, packet: &PacketRef<'_>) -> Result<GenericAudioBufferRef<'_>> {
-        // (Lookahead::decode clears the buffer on every error path: lib.rs:190-198)
-        self.la.decode(&mut self.batch, packet)?;
-        Ok(DecoderBatch::buffer(&self.batch))
-    }
-
-    fn finalize(&mut self) -> FinalizeResult {
-        Default::default()
-    }
-
-    fn last_decoded(&self) -> GenericAudioBufferRef<'_> {
-        DecoderBatch::buffer(&self.batch)
-    }
-}
-
-impl RegisterableAudioDecoder for HipAdpcmDecoder {
-    fn try_registry_new(params: &AudioCodecParameters, opts: &AudioDecoderOptions) -> Result<Box<dyn AudioDecoder>> {
-        // as the other decoders of this crate (decoder.rs): on the shared batcher if there is one; a shape, a device or memory this
-        // decoder cannot have sends the track to the decoder that was registered below
-        let built = match Pool::shared() {
-            Ok(pool) => Self::try_new_with_pool(params, opts, crate::DEFAULT_LOOKAHEAD, Some(pool)),
-            Err(_) => Self::try_new(params, opts, crate::DEFAULT_LOOKAHEAD),
-        };
-        match built {
-            Ok(decoder) => Ok(Box::new(decoder)),
-            Err(e) => crate::fallback::make(params, opts, e),
-        }
-    }
-
-    fn supported_codecs() -> &'static [SupportedAudioCodec] {
-        &[
-            support_audio_codec!(CODEC_ID_ADPCM_MS, "adpcm_ms", "Microsoft ADPCM (MI355X)"),
-            support_audio_codec!(CODEC_ID_ADPCM_IMA_WAV, "adpcm_ima_wav", "ADPCM IMA WAV (MI355X)"),
-            support_audio_codec!(CODEC_ID_ADPCM_IMA_QT, "adpcm_ima_qt", "ADPCM IMA QT (MI355X)"),
-        ]
     }
 }
 

@@ -13,7 +13,7 @@ use symphonia_core::errors::{decode_error, unsupported_error, Result};
 use symphonia_core::packet::PacketRef;
 use symphonia_core::support_audio_codec;
 
-use crate::ctx::{check, BatchSlot, Context, Pinned, Pool};
+use crate::ctx::{check, place_rows, Context, Pinned, Pool, SlotCycle};
 use crate::decoder::DecoderBatch;
 use crate::ffi;
 use crate::lookahead::{BatchCodec, Lookahead};
@@ -182,25 +182,36 @@ pub struct AlacBatch {
     ctx: Context,
     front: Box<dyn AlacFrontEnd>,
     nch: usize,
-    stride: usize,                      // words per element-channel slot of the current batch (its longest packet)
     words: Pinned<i32>,                 // [packet][plane][stride]
     desc: Vec<ffi::SymaccelAlacDesc>,   // [packet][plane]
     coeffs: Vec<i32>,                   // [packet][plane][32]
+    // the cross-stream batcher (SYMACCEL_BATCH_ALAC_PREDICT: a chain is an element channel, units = the stream's frame length) through
+    // the slot cycle of ctx.rs: what follows the predictor is applied to a batch that came through it in place, in the page-locked slot
+    slots: SlotCycle<AlacIndex>,
+    buf: AudioBuffer<i32>,
+}
+
+/// Where `publish` finds a packet in its batch, and what is left to do to it.
+pub struct AlacIndex {
+    stride: usize,  // words per element-channel slot (direct: the batch's longest packet; through the batcher: the stream's frame length)
     lens: Vec<usize>,
     pairs: Vec<Vec<AlacPair>>,
     tails: Vec<Vec<AlacTail>>,
     shifts: Vec<u32>,
-    // the cross-stream batcher (SYMACCEL_BATCH_ALAC_PREDICT: a chain is an element channel, units = the stream's frame length): `cur`
-    // holds the batch being handed out -- what follows the predictor is applied in place in the page-locked slot --, `next` the one
-    // submitted ahead
-    pool: Option<Arc<Pool>>,
-    cur: Option<BatchSlot>,
-    next: Option<BatchSlot>,
-    next_lens: Vec<usize>,
-    next_pairs: Vec<Vec<AlacPair>>,
-    next_tails: Vec<Vec<AlacTail>>,
-    next_shifts: Vec<u32>,
-    buf: AudioBuffer<i32>,
+}
+
+const NO_DESC: ffi::SymaccelAlacDesc = ffi::SymaccelAlacDesc { mode: 0, lpc_order: 0, shift: 0, bps: 32 };
+
+impl AlacBatch {
+    fn index_of(batch: &[ParsedAlac], stride: usize) -> AlacIndex {
+        AlacIndex {
+            stride,
+            lens: batch.iter().map(|p| p.frames).collect(),
+            pairs: batch.iter().map(|p| p.pairs.clone()).collect(),
+            tails: batch.iter().map(|p| p.tails.clone()).collect(),
+            shifts: batch.iter().map(|p| p.out_shift).collect(),
+        }
+    }
 }
 
 impl BatchCodec for AlacBatch {
@@ -215,86 +226,69 @@ impl BatchCodec for AlacBatch {
     }
 
     fn transform(&mut self, batch: &[ParsedAlac]) -> Result<()> {
-        // (a batch that came through the batcher is done with: this one is published from `words`)
-        if let (Some(pool), Some(old)) = (self.pool.clone(), self.cur.take()) {
-            pool.release(old);
-        }
         // Packets may differ in length (the last one of a stream): every element channel gets a slot of the batch's longest
         // packet, zero-padded -- predicting the padding is harmless, it is never read back.
-        let k = batch.len();
-        self.stride = batch.iter().map(|p| p.frames).max().unwrap_or(0);
-        self.lens.clear();
-        self.pairs.clear();
-        self.tails.clear();
-        self.shifts.clear();
+        let (k, nch) = (batch.len(), self.nch);
+        let stride = batch.iter().map(|p| p.frames).max().unwrap_or(0);
+        // (a batch that came through the batcher is done with: this one is published from `words`)
+        self.slots.start_direct(Self::index_of(batch, stride));
         let words = self.words.as_mut_slice();
-        for (i, p) in batch.iter().enumerate() {
-            for c in 0..self.nch {
-                let slot = (i * self.nch + c) * self.stride;
-                words[slot..slot + p.frames].copy_from_slice(&p.words[c * p.frames..(c + 1) * p.frames]);
-                words[slot + p.frames..slot + self.stride].fill(0);
-                self.desc[i * self.nch + c] = p.desc[c];
-                self.coeffs[(i * self.nch + c) * 32..(i * self.nch + c + 1) * 32].copy_from_slice(&p.coeffs[c * 32..(c + 1) * 32]);
-            }
-            self.lens.push(p.frames);
-            self.pairs.push(p.pairs.clone());
-            self.tails.push(p.tails.clone());
-            self.shifts.push(p.out_shift);
-        }
-        if self.stride == 0 {
+        place_rows(words, batch, nch, stride, 0, |p| p.words.as_slice());
+        place_rows(&mut self.desc, batch, nch, 1, NO_DESC, |p| p.desc.as_slice());
+        place_rows(&mut self.coeffs, batch, nch, 32, 0, |p| p.coeffs.as_slice());
+        if stride == 0 {
             return Ok(());
         }
         // SAFETY: `words`, `desc` and `coeffs` cover k * nch element channels of `stride` words (sized for max_batch packets of
         // the stream's frame length).
         check(
-            unsafe {
-                ffi::symaccel_alac_predict(self.ctx.raw(), words.as_mut_ptr(), self.desc.as_ptr(), self.coeffs.as_ptr(), k * self.nch, self.stride)
-            },
+            unsafe { ffi::symaccel_alac_predict(self.ctx.raw(), words.as_mut_ptr(), self.desc.as_ptr(), self.coeffs.as_ptr(), k * nch, stride) },
             self.ctx.raw(),
         )
     }
 
     fn publish(&mut self, i: usize) {
-        let n = self.lens[i];
-        self.buf.clear();
-        self.buf.render_uninit(Some(n));
         // the predicted element channels: in the batcher's slot (in place: the result plane IS input plane 0), or in this decoder's buffer
-        let words: &mut [i32] = match &mut self.cur {
+        let (ix, slot) = self.slots.parts_mut();
+        let words: &mut [i32] = match slot {
             Some(slot) => slot.input::<i32>(0),
             None => self.words.as_mut_slice(),
         };
-        let base = i * self.nch * self.stride;
+        let (n, stride) = (ix.lens[i], ix.stride);
+        self.buf.clear();
+        self.buf.render_uninit(Some(n));
+        let base = i * self.nch * stride;
         // what follows the predictor, in the decoder's order (lib.rs:541-598, 409-414), on this packet's slots
-        for pair in &self.pairs[i] {
+        for pair in &ix.pairs[i] {
             for t in 0..n {
-                let s0 = words[base + pair.plane0 * self.stride + t];
-                let s1 = words[base + pair.plane1 * self.stride + t];
+                let s0 = words[base + pair.plane0 * stride + t];
+                let s1 = words[base + pair.plane1 * stride + t];
                 let left = s0 + s1 - ((s1 * pair.weight) >> pair.shift); // lib.rs:668-669
-                words[base + pair.plane0 * self.stride + t] = left;
-                words[base + pair.plane1 * self.stride + t] = left - s1;
+                words[base + pair.plane0 * stride + t] = left;
+                words[base + pair.plane1 * stride + t] = left - s1;
             }
         }
-        for tail in &self.tails[i] {
+        for tail in &ix.tails[i] {
             for t in 0..n {
                 match tail.plane1 {
                     Some(plane1) => {
-                        let a = base + tail.plane0 * self.stride + t;
-                        let b = base + plane1 * self.stride + t;
+                        let a = base + tail.plane0 * stride + t;
+                        let b = base + plane1 * stride + t;
                         words[a] = (words[a] << tail.shift) | tail.bits[2 * t] as i32;
                         words[b] = (words[b] << tail.shift) | tail.bits[2 * t + 1] as i32;
                     }
                     None => {
-                        let a = base + tail.plane0 * self.stride + t;
+                        let a = base + tail.plane0 * stride + t;
                         words[a] = (words[a] << tail.shift) | tail.bits[t] as i32;
                     }
                 }
             }
         }
-        let shift = self.shifts[i];
+        let shift = ix.shifts[i];
         for c in 0..self.nch {
             if let Some(plane) = self.buf.plane_mut(c) {
                 for t in 0..n {
-                    plane[t] = words[base + c * self.stride + t].wrapping_shl(shift);
+                    plane[t] = words[base + c * stride + t].wrapping_shl(shift);
                 }
             }
         }
@@ -307,107 +301,35 @@ impl BatchCodec for AlacBatch {
     }
 
     fn pooled(&self) -> bool {
-        self.pool.is_some()
+        self.slots.pooled()
     }
 
     /// The stream's next batch goes to the process-wide batcher: residuals, predictors and coefficients are written straight into a
     /// page-locked slot; the device predicts in place, in one launch with the other streams' batches.
     fn submit(&mut self, batch: &[ParsedAlac]) -> Result<()> {
-        let Some(pool) = self.pool.clone() else {
-            return unsupported_error("alac: no batcher");
-        };
-        if batch.is_empty() || self.next.is_some() {
-            return unsupported_error("alac: one batch at a time");
-        }
         let (k, nch) = (batch.len(), self.nch);
         let stride = self.front.max_frames(); // (the same for every batch of the stream: the group key)
-        if stride == 0 {
-            return unsupported_error("alac: empty packets");
+        if k == 0 || stride == 0 {
+            return unsupported_error("alac: an empty batch, or empty packets");
         }
-        let mut slot = pool.reserve(ffi::SYMACCEL_BATCH_ALAC_PREDICT as i32, 0, k * nch, stride)?;
-        {
-            let words = slot.input::<i32>(0);
-            for (i, p) in batch.iter().enumerate() {
-                for c in 0..nch {
-                    let at = (i * nch + c) * stride;
-                    words[at..at + p.frames].copy_from_slice(&p.words[c * p.frames..(c + 1) * p.frames]);
-                    words[at + p.frames..at + stride].fill(0);
-                }
-            }
-        }
-        {
-            let desc = slot.input::<ffi::SymaccelAlacDesc>(1);
-            for (i, p) in batch.iter().enumerate() {
-                for c in 0..nch {
-                    desc[i * nch + c] = p.desc[c];
-                }
-            }
-        }
-        {
-            let coeffs = slot.input::<i32>(2);
-            for (i, p) in batch.iter().enumerate() {
-                for c in 0..nch {
-                    coeffs[(i * nch + c) * 32..(i * nch + c + 1) * 32].copy_from_slice(&p.coeffs[c * 32..(c + 1) * 32]);
-                }
-            }
-        }
-        self.next_lens.clear();
-        self.next_pairs.clear();
-        self.next_tails.clear();
-        self.next_shifts.clear();
-        for p in batch {
-            self.next_lens.push(p.frames);
-            self.next_pairs.push(p.pairs.clone());
-            self.next_tails.push(p.tails.clone());
-            self.next_shifts.push(p.out_shift);
-        }
-        if let Err(e) = pool.commit(&mut slot) {
-            pool.release(slot);
-            return Err(e);
-        }
-        self.next = Some(slot);
-        Ok(())
+        self.slots.submit(ffi::SYMACCEL_BATCH_ALAC_PREDICT as i32, 0, k * nch, stride, Self::index_of(batch, stride), |slot| {
+            place_rows(slot.input::<i32>(0), batch, nch, stride, 0, |p| p.words.as_slice());
+            place_rows(slot.input::<ffi::SymaccelAlacDesc>(1), batch, nch, 1, NO_DESC, |p| p.desc.as_slice());
+            place_rows(slot.input::<i32>(2), batch, nch, 32, 0, |p| p.coeffs.as_slice());
+            Ok(())
+        })
     }
 
     fn collect(&mut self) -> Result<()> {
-        let (Some(pool), Some(mut slot)) = (self.pool.clone(), self.next.take()) else {
-            return unsupported_error("alac: nothing was submitted");
-        };
-        if let Err(e) = pool.wait(&mut slot) {
-            pool.release(slot);
-            return Err(e);
-        }
-        if let Some(old) = self.cur.take() {
-            pool.release(old);
-        }
-        self.cur = Some(slot);
-        self.stride = self.front.max_frames();
-        std::mem::swap(&mut self.lens, &mut self.next_lens);
-        std::mem::swap(&mut self.pairs, &mut self.next_pairs);
-        std::mem::swap(&mut self.tails, &mut self.next_tails);
-        std::mem::swap(&mut self.shifts, &mut self.next_shifts);
-        Ok(())
+        self.slots.collect(|_| {})
     }
 
     fn hint(&mut self) {
-        if let Some(pool) = &self.pool {
-            pool.hint();
-        }
+        self.slots.hint();
     }
 
     fn abandon(&mut self) {
-        if let (Some(pool), Some(slot)) = (self.pool.clone(), self.next.take()) {
-            pool.release(slot);
-        }
-    }
-}
-
-impl Drop for AlacBatch {
-    fn drop(&mut self) {
-        BatchCodec::abandon(self);
-        if let (Some(pool), Some(slot)) = (self.pool.clone(), self.cur.take()) {
-            pool.release(slot);
-        }
+        self.slots.abandon();
     }
 }
 
@@ -421,22 +343,12 @@ crate::hip_decoder!(
     HipAlacDecoder,
     AlacBatch,
     ParsedAlac,
-    crate::frontends::alac_front_end,
     &[support_audio_codec!(CODEC_ID_ALAC, "alac", "Apple Lossless Audio Codec (MI355X predictors)")],
     "ALAC decoder with the same observable behaviour as `symphonia_codec_alac::AlacDecoder`."
 );
+crate::hip_decoder!(@new HipAlacDecoder, crate::frontends::alac_front_end, Box<dyn AlacFrontEnd>);
 
 impl HipAlacDecoder {
-    pub fn try_new(params: &AudioCodecParameters, opts: &AudioDecoderOptions, front: Box<dyn AlacFrontEnd>, max_batch: usize) -> Result<Self> {
-        Self::try_new_with_pool(params, opts, front, max_batch, None)
-    }
-
-    /// The same decoder submitting to the process-wide cross-stream batcher (`Pool::shared()`): the element channels of every open
-    /// ALAC stream with this frame length are predicted in one launch (csrc/batcher.cpp, SYMACCEL_BATCH_ALAC_PREDICT).
-    pub fn try_new_pooled(params: &AudioCodecParameters, opts: &AudioDecoderOptions, front: Box<dyn AlacFrontEnd>, max_batch: usize) -> Result<Self> {
-        Self::try_new_with_pool(params, opts, front, max_batch, Some(Pool::shared()?))
-    }
-
     pub fn try_new_with_pool(
         _params: &AudioCodecParameters,
         _opts: &AudioDecoderOptions,
@@ -457,21 +369,10 @@ impl HipAlacDecoder {
                 ctx: Context::new(0)?,
                 front,
                 nch,
-                stride: max_frames,
                 words: Pinned::new(max_batch * nch * max_frames)?,
-                desc: vec![ffi::SymaccelAlacDesc { mode: 0, lpc_order: 0, shift: 0, bps: 32 }; max_batch * nch],
+                desc: vec![NO_DESC; max_batch * nch],
                 coeffs: vec![0; max_batch * nch * 32],
-                lens: Vec::with_capacity(max_batch),
-                pairs: Vec::with_capacity(max_batch),
-                tails: Vec::with_capacity(max_batch),
-                shifts: Vec::with_capacity(max_batch),
-                pool,
-                cur: None,
-                next: None,
-                next_lens: Vec::with_capacity(max_batch),
-                next_pairs: Vec::with_capacity(max_batch),
-                next_tails: Vec::with_capacity(max_batch),
-                next_shifts: Vec::with_capacity(max_batch),
+                slots: SlotCycle::new(pool, AlacBatch::index_of(&[], max_frames)),
                 buf: AudioBuffer::new(AudioSpec::new(rate, channels), max_frames),
             },
             la: Lookahead::new(max_batch),

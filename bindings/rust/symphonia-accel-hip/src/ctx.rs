@@ -1,9 +1,10 @@
-//! Safe ownership of a `symaccel_ctx` and of page-locked batch buffers.
+//! Safe ownership of a `symaccel_ctx` and of page-locked batch buffers: `Context`, the process-wide `Pool`, a `BatchSlot` of the
+//! cross-stream batcher and the `SlotCycle` through which the seven slot codecs hold theirs (AAC uses the copying ticket path), `Pinned`.
 use std::ffi::CStr;
 use std::ptr;
 use std::sync::{Arc, Mutex};
 
-use symphonia_core::errors::{Error, Result};
+use symphonia_core::errors::{unsupported_error, Error, Result};
 
 use crate::ffi;
 
@@ -201,8 +202,14 @@ impl Pool {
     /// Block until the submission's results are in its slot.  The status is this submission's own: a batch whose descriptors do
     /// not add up fails alone, the neighbours of its launch do not (include/symaccel.h, "Status is kept PER TICKET").
     pub fn wait(&self, slot: &mut BatchSlot) -> Result<()> {
+        let status = self.wait_raw(slot);
+        self.check(status)
+    }
+
+    /// `wait` before the status is judged (`check` panics on INVALID_ARG: a caller that owns the slot gives it back first).
+    fn wait_raw(&self, slot: &mut BatchSlot) -> i32 {
         // SAFETY: a live, committed ticket; the slot record is filled in again with the same pointers.
-        self.check(unsafe { ffi::symaccel_batcher_wait(self.batcher, slot.ticket, &mut slot.raw) })
+        unsafe { ffi::symaccel_batcher_wait(self.batcher, slot.ticket, &mut slot.raw) }
     }
 
     /// Give the slot back (a reservation that was never committed runs as zeros with its group; nobody looks at the result).
@@ -263,6 +270,146 @@ impl Drop for Pool {
     fn drop(&mut self) {
         // SAFETY: created by symaccel_batcher_create, destroyed once, before its context.
         unsafe { ffi::symaccel_batcher_destroy(self.batcher) };
+    }
+}
+
+/// The batcher-slot cycle of a pooled codec: the one place where `BatchSlot`s are reserved, committed, waited for and released.
+///
+/// A pooled codec has at most two slots at a time: the one whose batch is being handed out (`publish` reads the PCM where the device
+/// left it) and the one submitted ahead.  The slots are page-locked memory that every stream of the process shares, so the rule is:
+/// every slot is released exactly once, on every path.  `SlotCycle` owns the pool handle and both slots and is the only caller of
+/// `Pool::reserve` / `commit` / `wait` / `release`; a codec supplies what is its own -- the kind, the parameter, the sizes, the fill of
+/// the input planes, the read-back of the state planes -- and the per-batch index `M` (block sizes, trims, offsets: whatever its
+/// `publish` needs to find a packet in the batch), which travels WITH the slot of its batch and becomes current when that slot does.
+pub struct SlotCycle<M> {
+    pool: Option<Arc<Pool>>,
+    /// the index of the batch being handed out, and the slot it came in (`None`: a direct batch, served from the codec's own buffers)
+    index: M,
+    cur: Option<BatchSlot>,
+    /// the batch submitted ahead and its index
+    next: Option<(BatchSlot, M)>,
+}
+
+impl<M> SlotCycle<M> {
+    /// `index`: what `index()` answers before the first batch (an empty one).
+    pub fn new(pool: Option<Arc<Pool>>, index: M) -> Self {
+        SlotCycle { pool, index, cur: None, next: None }
+    }
+
+    /// Does the codec submit to the shared batcher?
+    pub fn pooled(&self) -> bool {
+        self.pool.is_some()
+    }
+
+    /// The index of the batch being handed out.
+    pub fn index(&self) -> &M {
+        &self.index
+    }
+
+    /// The result plane of the batch being handed out, if it came through the batcher (read in place: nothing is copied).
+    pub fn out<T: Copy>(&self) -> Option<&[T]> {
+        match &self.cur {
+            Some(slot) => Some(slot.out::<T>()),
+            None => None,
+        }
+    }
+
+    /// The current index together with the current slot, for a codec that finishes a packet in place in the slot (ALAC).
+    pub fn parts_mut(&mut self) -> (&M, Option<&mut BatchSlot>) {
+        (&self.index, self.cur.as_mut())
+    }
+
+    /// A batch the codec transforms on its own becomes current: a slot left from the batcher is done with and goes back.
+    pub fn start_direct(&mut self, index: M) {
+        self.release_current();
+        self.index = index;
+    }
+
+    /// `reserve` -> `fill` -> `commit`.  Refused without a pool and while a batch is submitted.  Whatever fails after `reserve`, the
+    /// slot goes back and nothing is pending.
+    pub fn submit<F: FnOnce(&mut BatchSlot) -> Result<()>>(&mut self, kind: i32, param: i32, n_chains: usize, units: usize, index: M, fill: F) -> Result<()> {
+        let Some(pool) = self.pool.clone() else {
+            return unsupported_error("no batcher");
+        };
+        if self.next.is_some() {
+            return unsupported_error("one batch at a time");
+        }
+        let mut slot = pool.reserve(kind, param, n_chains, units)?;
+        let filled = match fill(&mut slot) {
+            Ok(()) => pool.commit(&mut slot),
+            Err(e) => Err(e),
+        };
+        if let Err(e) = filled {
+            pool.release(slot);
+            return Err(e);
+        }
+        self.next = Some((slot, index));
+        Ok(())
+    }
+
+    /// Wait for the submitted batch.  On error its slot goes back and the current batch stays current.  On success `read_back` sees the
+    /// slot (its state planes hold the state after the batch), the old current slot goes back, the new one and its index are current.
+    pub fn collect<F: FnOnce(&mut BatchSlot)>(&mut self, read_back: F) -> Result<()> {
+        let (Some(pool), Some((mut slot, index))) = (self.pool.clone(), self.next.take()) else {
+            return unsupported_error("nothing was submitted");
+        };
+        let status = pool.wait_raw(&mut slot);
+        if status < 0 {
+            // (back BEFORE the status is judged: INVALID_ARG is the panic class of `check`, and a panic must not keep a slot either)
+            pool.release(slot);
+            return pool.check(status);
+        }
+        read_back(&mut slot);
+        self.release_current();
+        self.cur = Some(slot);
+        self.index = index;
+        Ok(())
+    }
+
+    /// "Results will be wanted soon" (`Pool::hint`).
+    pub fn hint(&self) {
+        if let Some(pool) = &self.pool {
+            pool.hint();
+        }
+    }
+
+    /// Drop the submitted batch unseen.
+    pub fn abandon(&mut self) {
+        if let (Some(pool), Some((slot, _))) = (self.pool.clone(), self.next.take()) {
+            pool.release(slot);
+        }
+    }
+
+    fn release_current(&mut self) {
+        if let (Some(pool), Some(slot)) = (self.pool.clone(), self.cur.take()) {
+            pool.release(slot);
+        }
+    }
+
+    /// Both slots go back: what `Drop` does.
+    pub fn release_all(&mut self) {
+        self.abandon();
+        self.release_current();
+    }
+}
+
+impl<M> Drop for SlotCycle<M> {
+    fn drop(&mut self) {
+        self.release_all();
+    }
+}
+
+/// One plane of a batch in the packet-major layout that the FLAC and ALAC entry points and their batcher slots share: row `i * nch + c`
+/// of `dst` (rows of `pitch` elements) is channel `c` of packet `i`'s plane, `zero` behind a shorter one.
+pub(crate) fn place_rows<P, T: Copy>(dst: &mut [T], batch: &[P], nch: usize, pitch: usize, zero: T, plane: impl Fn(&P) -> &[T]) {
+    for (i, p) in batch.iter().enumerate() {
+        let src = plane(p);
+        let w = src.len() / nch;
+        for c in 0..nch {
+            let at = (i * nch + c) * pitch;
+            dst[at..at + w].copy_from_slice(&src[c * w..(c + 1) * w]);
+            dst[at + w..at + pitch].fill(zero);
+        }
     }
 }
 

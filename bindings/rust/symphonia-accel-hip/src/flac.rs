@@ -11,7 +11,7 @@ use symphonia_core::errors::{decode_error, unsupported_error, Result};
 use symphonia_core::packet::PacketRef;
 use symphonia_core::support_audio_codec;
 
-use crate::ctx::{check, BatchSlot, Context, Pinned, Pool};
+use crate::ctx::{check, place_rows, Context, Pinned, Pool, SlotCycle};
 use crate::decoder::DecoderBatch;
 use crate::ffi;
 use crate::lookahead::{BatchCodec, Lookahead};
@@ -160,23 +160,35 @@ pub struct FlacBatch {
     ctx: Context,
     front: Box<dyn FlacFrontEnd>,
     nch: usize,
-    stride: usize,                      // words per subframe slot of the current batch (its largest block size)
     words: Pinned<i32>,                 // [packet][channel][stride]
     desc: Vec<ffi::SymaccelFlacDesc>,   // [packet][channel]
     coeffs: Vec<i32>,                   // [packet][channel][32]
-    lens: Vec<usize>,                   // block size of each packet of the batch
+    // the cross-stream batcher (SYMACCEL_BATCH_FLAC_RESTORE: a chain is a subframe, units = the stream's maximum block size, so the
+    // batches of every FLAC stream with that block size share launches whatever their lengths) through the slot cycle of ctx.rs: the
+    // restored words of a batch that came through it are read where the device left them, in the page-locked slot
+    slots: SlotCycle<FlacIndex>,
+    buf: AudioBuffer<i32>,
+}
+
+/// Where `publish` finds a packet in its batch.
+pub struct FlacIndex {
+    stride: usize,     // words per subframe slot (direct: the batch's largest block size; through the batcher: the stream's)
+    lens: Vec<usize>,  // block size of each packet of the batch
     modes: Vec<u8>,
     shifts: Vec<u32>,
-    // the cross-stream batcher (SYMACCEL_BATCH_FLAC_RESTORE: a chain is a subframe, units = the stream's maximum block size, so the
-    // batches of every FLAC stream with that block size share launches whatever their lengths): `cur` holds the batch being handed
-    // out -- its restored words are read where the device left them, in the page-locked slot --, `next` the one submitted ahead
-    pool: Option<Arc<Pool>>,
-    cur: Option<BatchSlot>,
-    next: Option<BatchSlot>,
-    next_lens: Vec<usize>,
-    next_modes: Vec<u8>,
-    next_shifts: Vec<u32>,
-    buf: AudioBuffer<i32>,
+}
+
+const NO_DESC: ffi::SymaccelFlacDesc = ffi::SymaccelFlacDesc { kind: 0, order: 0, shift: 0, wasted_bits: 0 };
+
+impl FlacBatch {
+    fn index_of(batch: &[ParsedFlac], nch: usize, stride: usize) -> FlacIndex {
+        FlacIndex {
+            stride,
+            lens: batch.iter().map(|p| p.blocksize).collect(),
+            modes: batch.iter().map(|p| if nch == 2 { p.pair_mode } else { 0 }).collect(),
+            shifts: batch.iter().map(|p| p.out_shift).collect(),
+        }
+    }
 }
 
 impl BatchCodec for FlacBatch {
@@ -191,61 +203,42 @@ impl BatchCodec for FlacBatch {
     }
 
     fn transform(&mut self, batch: &[ParsedFlac]) -> Result<()> {
-        // (a batch that came through the batcher is done with: this one is published from `words`)
-        if let (Some(pool), Some(old)) = (self.pool.clone(), self.cur.take()) {
-            pool.release(old);
-        }
         // Block sizes may differ (the last frame of a stream, variable-block-size streams): every subframe gets a slot
         // of the batch's largest block size, zero-padded -- predicting the padding is harmless, it is never read back.
-        let k = batch.len();
-        self.stride = batch.iter().map(|p| p.blocksize).max().unwrap_or(0);
-        self.lens.clear();
-        self.modes.clear();
-        self.shifts.clear();
+        let (k, nch) = (batch.len(), self.nch);
+        let stride = batch.iter().map(|p| p.blocksize).max().unwrap_or(0);
+        // (a batch that came through the batcher is done with: this one is published from `words`)
+        self.slots.start_direct(Self::index_of(batch, nch, stride));
         let words = self.words.as_mut_slice();
-        for (i, p) in batch.iter().enumerate() {
-            for c in 0..self.nch {
-                let slot = (i * self.nch + c) * self.stride;
-                words[slot..slot + p.blocksize].copy_from_slice(&p.words[c * p.blocksize..(c + 1) * p.blocksize]);
-                words[slot + p.blocksize..slot + self.stride].fill(0);
-                self.desc[i * self.nch + c] = p.desc[c];
-                self.coeffs[(i * self.nch + c) * 32..(i * self.nch + c + 1) * 32].copy_from_slice(&p.coeffs[c * 32..(c + 1) * 32]);
-            }
-            self.lens.push(p.blocksize);
-            self.modes.push(if self.nch == 2 { p.pair_mode } else { 0 });
-            self.shifts.push(p.out_shift);
-        }
+        place_rows(words, batch, nch, stride, 0, |p| p.words.as_slice());
+        place_rows(&mut self.desc, batch, nch, 1, NO_DESC, |p| p.desc.as_slice());
+        place_rows(&mut self.coeffs, batch, nch, 32, 0, |p| p.coeffs.as_slice());
         // SAFETY: `words`, `desc` and `coeffs` cover k * nch subframes of `stride` words (sized for max_batch frames of
         // the stream's maximum block size).
         check(
-            unsafe {
-                ffi::symaccel_flac_restore(self.ctx.raw(), words.as_mut_ptr(), self.desc.as_ptr(), self.coeffs.as_ptr(), k * self.nch, self.stride)
-            },
+            unsafe { ffi::symaccel_flac_restore(self.ctx.raw(), words.as_mut_ptr(), self.desc.as_ptr(), self.coeffs.as_ptr(), k * nch, stride) },
             self.ctx.raw(),
         )
     }
 
     fn publish(&mut self, i: usize) {
-        let n = self.lens[i];
+        let ix = self.slots.index();
+        let (n, stride, mode, shift) = (ix.lens[i], ix.stride, ix.modes[i], ix.shifts[i]);
         self.buf.clear();
         self.buf.render_uninit(Some(n));
         // the restored subframes: in the batcher's slot (zero-copy: the device wrote them there), or in this decoder's own buffer
-        let words: &[i32] = match &self.cur {
-            Some(slot) => slot.out::<i32>(),
-            None => self.words.as_slice(),
-        };
-        let base = i * self.nch * self.stride;
+        let words: &[i32] = self.slots.out::<i32>().unwrap_or(self.words.as_slice());
+        let base = i * self.nch * stride;
         // decorrelation + left-justification of ONE frame is 2 * blocksize operations: done here on the copy out (the
         // batched device form, symaccel_flac_restore_stereo_device, is for callers that keep the PCM on the GPU)
-        let shift = self.shifts[i];
         for c in 0..self.nch {
             if let Some(plane) = self.buf.plane_mut(c) {
                 for t in 0..n {
-                    let own = words[base + c * self.stride + t];
-                    let v = if self.nch == 2 && self.modes[i] != 0 {
+                    let own = words[base + c * stride + t];
+                    let v = if self.nch == 2 && mode != 0 {
                         let a = words[base + t];
-                        let b = words[base + self.stride + t];
-                        match (self.modes[i], c) {
+                        let b = words[base + stride + t];
+                        match (mode, c) {
                             (1, 1) => a.wrapping_sub(b),                                  // left/side: right = left - side
                             (2, _) => {
                                 let mid = (a << 1) | (b & 1);                             // decoder.rs:38-73
@@ -271,101 +264,35 @@ impl BatchCodec for FlacBatch {
     }
 
     fn pooled(&self) -> bool {
-        self.pool.is_some()
+        self.slots.pooled()
     }
 
-    /// The stream's next batch goes to the process-wide batcher: the subframes are written straight into a page-locked slot
-    /// (`Pool::reserve` -> fill -> `commit`); the device restores them in place, in one launch with the other streams' batches.
+    /// The stream's next batch goes to the process-wide batcher: the subframes are written straight into a page-locked slot; the
+    /// device restores them in place, in one launch with the other streams' batches.
     fn submit(&mut self, batch: &[ParsedFlac]) -> Result<()> {
-        let Some(pool) = self.pool.clone() else {
-            return unsupported_error("flac: no batcher");
-        };
-        if batch.is_empty() || self.next.is_some() {
-            return unsupported_error("flac: one batch at a time");
+        if batch.is_empty() {
+            return unsupported_error("flac: an empty batch");
         }
         let (k, nch) = (batch.len(), self.nch);
         let stride = self.front.max_blocksize(); // (the same for every batch of the stream: the group key)
-        let mut slot = pool.reserve(ffi::SYMACCEL_BATCH_FLAC_RESTORE as i32, 0, k * nch, stride)?;
-        self.next_lens.clear();
-        self.next_modes.clear();
-        self.next_shifts.clear();
-        {
-            let words = slot.input::<i32>(0);
-            for (i, p) in batch.iter().enumerate() {
-                for c in 0..nch {
-                    let at = (i * nch + c) * stride;
-                    words[at..at + p.blocksize].copy_from_slice(&p.words[c * p.blocksize..(c + 1) * p.blocksize]);
-                    words[at + p.blocksize..at + stride].fill(0);
-                }
-            }
-        }
-        {
-            let desc = slot.input::<ffi::SymaccelFlacDesc>(1);
-            for (i, p) in batch.iter().enumerate() {
-                for c in 0..nch {
-                    desc[i * nch + c] = p.desc[c];
-                }
-            }
-        }
-        {
-            let coeffs = slot.input::<i32>(2);
-            for (i, p) in batch.iter().enumerate() {
-                for c in 0..nch {
-                    coeffs[(i * nch + c) * 32..(i * nch + c + 1) * 32].copy_from_slice(&p.coeffs[c * 32..(c + 1) * 32]);
-                }
-            }
-        }
-        for p in batch {
-            self.next_lens.push(p.blocksize);
-            self.next_modes.push(if nch == 2 { p.pair_mode } else { 0 });
-            self.next_shifts.push(p.out_shift);
-        }
-        if let Err(e) = pool.commit(&mut slot) {
-            pool.release(slot);
-            return Err(e);
-        }
-        self.next = Some(slot);
-        Ok(())
+        self.slots.submit(ffi::SYMACCEL_BATCH_FLAC_RESTORE as i32, 0, k * nch, stride, Self::index_of(batch, nch, stride), |slot| {
+            place_rows(slot.input::<i32>(0), batch, nch, stride, 0, |p| p.words.as_slice());
+            place_rows(slot.input::<ffi::SymaccelFlacDesc>(1), batch, nch, 1, NO_DESC, |p| p.desc.as_slice());
+            place_rows(slot.input::<i32>(2), batch, nch, 32, 0, |p| p.coeffs.as_slice());
+            Ok(())
+        })
     }
 
     fn collect(&mut self) -> Result<()> {
-        let (Some(pool), Some(mut slot)) = (self.pool.clone(), self.next.take()) else {
-            return unsupported_error("flac: nothing was submitted");
-        };
-        if let Err(e) = pool.wait(&mut slot) {
-            pool.release(slot);
-            return Err(e);
-        }
-        if let Some(old) = self.cur.take() {
-            pool.release(old);
-        }
-        self.cur = Some(slot);
-        self.stride = self.front.max_blocksize();
-        std::mem::swap(&mut self.lens, &mut self.next_lens);
-        std::mem::swap(&mut self.modes, &mut self.next_modes);
-        std::mem::swap(&mut self.shifts, &mut self.next_shifts);
-        Ok(())
+        self.slots.collect(|_| {})
     }
 
     fn hint(&mut self) {
-        if let Some(pool) = &self.pool {
-            pool.hint();
-        }
+        self.slots.hint();
     }
 
     fn abandon(&mut self) {
-        if let (Some(pool), Some(slot)) = (self.pool.clone(), self.next.take()) {
-            pool.release(slot);
-        }
-    }
-}
-
-impl Drop for FlacBatch {
-    fn drop(&mut self) {
-        BatchCodec::abandon(self);
-        if let (Some(pool), Some(slot)) = (self.pool.clone(), self.cur.take()) {
-            pool.release(slot);
-        }
+        self.slots.abandon();
     }
 }
 
@@ -379,22 +306,12 @@ crate::hip_decoder!(
     HipFlacDecoder,
     FlacBatch,
     ParsedFlac,
-    crate::frontends::flac_front_end,
     &[support_audio_codec!(CODEC_ID_FLAC, "flac", "Free Lossless Audio Codec (MI355X predictors)")],
     "FLAC decoder with the same observable behaviour as `symphonia_bundle_flac::FlacDecoder` (verification off)."
 );
+crate::hip_decoder!(@new HipFlacDecoder, crate::frontends::flac_front_end, Box<dyn FlacFrontEnd>);
 
 impl HipFlacDecoder {
-    pub fn try_new(params: &AudioCodecParameters, opts: &AudioDecoderOptions, front: Box<dyn FlacFrontEnd>, max_batch: usize) -> Result<Self> {
-        Self::try_new_with_pool(params, opts, front, max_batch, None)
-    }
-
-    /// The same decoder submitting to the process-wide cross-stream batcher (`Pool::shared()`): with many streams open, the
-    /// subframes of all of them are restored in one launch (csrc/batcher.cpp, SYMACCEL_BATCH_FLAC_RESTORE).
-    pub fn try_new_pooled(params: &AudioCodecParameters, opts: &AudioDecoderOptions, front: Box<dyn FlacFrontEnd>, max_batch: usize) -> Result<Self> {
-        Self::try_new_with_pool(params, opts, front, max_batch, Some(Pool::shared()?))
-    }
-
     pub fn try_new_with_pool(
         _params: &AudioCodecParameters,
         opts: &AudioDecoderOptions,
@@ -419,19 +336,10 @@ impl HipFlacDecoder {
                 ctx: Context::new(0)?,
                 front,
                 nch,
-                stride: max_bs,
                 words: Pinned::new(max_batch * nch * max_bs)?,
-                desc: vec![ffi::SymaccelFlacDesc { kind: 0, order: 0, shift: 0, wasted_bits: 0 }; max_batch * nch],
+                desc: vec![NO_DESC; max_batch * nch],
                 coeffs: vec![0; max_batch * nch * 32],
-                lens: Vec::with_capacity(max_batch),
-                modes: Vec::with_capacity(max_batch),
-                shifts: Vec::with_capacity(max_batch),
-                pool,
-                cur: None,
-                next: None,
-                next_lens: Vec::with_capacity(max_batch),
-                next_modes: Vec::with_capacity(max_batch),
-                next_shifts: Vec::with_capacity(max_batch),
+                slots: SlotCycle::new(pool, FlacBatch::index_of(&[], nch, max_bs)),
                 buf: AudioBuffer::new(AudioSpec::new(rate, channels), max_bs),
             },
             la: Lookahead::new(max_batch),

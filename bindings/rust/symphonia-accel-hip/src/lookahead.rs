@@ -233,7 +233,7 @@ pub trait BatchCodec {
     fn abandon(&mut self) {}
 }
 
-/// Batching state shared by the five decoders.
+/// The batching state of a decoder: every one of the crate's eight has one (`hip_decoder!`, decoder.rs).
 pub struct Lookahead<P> {
     /// the packets of the last batch, parsed, and their pts, in order; `head` = the next one to hand out
     parsed: Vec<P>,

@@ -15,7 +15,7 @@ use symphonia_core::errors::{decode_error, unsupported_error, Result};
 use symphonia_core::packet::PacketRef;
 use symphonia_core::support_audio_codec;
 
-use crate::ctx::{check, BatchSlot, Context, Pinned, Pool};
+use crate::ctx::{check, Context, Pinned, Pool, SlotCycle};
 use crate::decoder::DecoderBatch;
 use crate::ffi;
 use crate::lookahead::{BatchCodec, Lookahead};
@@ -287,19 +287,72 @@ pub struct MpaBatch {
     pcm: Pinned<f32>,                 // [channel][granule of the batch][576]
     quant: Pinned<i16>,               // the fused form: [channel][granule of the batch][576] Huffman samples,
     rq: Vec<ffi::SymaccelMp3Requant>, //   [channel][granule of the batch],
-    st: Vec<ffi::SymaccelMp3Stereo>,  //   [granule of the batch] (the one channel pair of a stereo stream)
-    first_granule: Vec<usize>,        // per packet of the batch: index of its first granule; one extra entry = total
-    trims: Vec<(usize, usize)>,       // per packet of the batch
-    // the cross-stream batcher (SYMACCEL_BATCH_MP3_DECODE, one stream per submission): `cur` holds the batch being handed out -- its PCM
-    // is read where the device left it, in the page-locked slot --, `next` the one submitted ahead (its state lands in `overlap` /
-    // `vvec` / `vfront` at collect)
-    pool: Option<Arc<Pool>>,
-    cur: Option<BatchSlot>,
-    next: Option<BatchSlot>,
-    next_first_granule: Vec<usize>,
-    next_trims: Vec<(usize, usize)>,
+    st: Vec<ffi::SymaccelMp3Stereo>,  //   [granule of the batch] (the one channel pair of a stream)
+    // the cross-stream batcher (SYMACCEL_BATCH_MP3_DECODE, one stream per submission) through the slot cycle of ctx.rs: the PCM of a
+    // batch that came through it is read where the device left it, in the page-locked slot; its state lands in `overlap` / `vvec` /
+    // `vfront` at collect
+    slots: SlotCycle<MpaIndex>,
     gapless: bool,
     buf: AudioBuffer<f32>,
+}
+
+/// Where `publish` finds a packet in its batch.
+pub struct MpaIndex {
+    first_granule: Vec<usize>,   // per packet of the batch: index of its first granule; one extra entry = total
+    trims: Vec<(usize, usize)>,  // per packet of the batch
+}
+
+const NO_STEREO: ffi::SymaccelMp3Stereo = ffi::SymaccelMp3Stereo { flags: 0, block_type: 0, is_mixed: 0, reserved: 0, rzero0: 0, rzero1: 0, scalefacs1: [0; 39], pad: 0 };
+
+impl MpaBatch {
+    fn index_of(batch: &[ParsedMpa]) -> MpaIndex {
+        let mut first_granule = Vec::with_capacity(batch.len() + 1);
+        let mut total = 0usize;
+        for p in batch {
+            first_granule.push(total);
+            total += p.n_granules;
+        }
+        first_granule.push(total);
+        MpaIndex { first_granule, trims: batch.iter().map(|p| p.trim).collect() }
+    }
+
+    /// One per-granule-channel plane of a batch in the chain-major layout the host entry points and the batcher's slot share: row
+    /// `c * total + first[i] + g` of `dst` (rows of `w` elements) is granule `g`, channel `c` of packet `i` (a packet hands its plane
+    /// over as [granule][channel]; one without the plane is skipped).
+    fn place<T: Copy>(dst: &mut [T], batch: &[ParsedMpa], first: &[usize], nch: usize, w: usize, plane: impl Fn(&ParsedMpa) -> Option<&[T]>) {
+        let total = first[batch.len()];
+        for (i, p) in batch.iter().enumerate() {
+            let Some(src) = plane(p) else { continue };
+            for g in 0..p.n_granules {
+                for c in 0..nch {
+                    let at = c * total + first[i] + g;
+                    dst[at * w..(at + 1) * w].copy_from_slice(&src[(g * nch + c) * w..(g * nch + c + 1) * w]);
+                }
+            }
+        }
+    }
+
+    /// The joint-stereo plane of a fused batch: one record per granule of the STREAM (all zeros for a mono stream).
+    fn place_stereo(st: &mut [ffi::SymaccelMp3Stereo], batch: &[ParsedMpa], first: &[usize], nch: usize) {
+        for (i, p) in batch.iter().enumerate() {
+            let Some(f) = &p.fused else { continue };
+            for g in 0..p.n_granules {
+                st[first[i] + g] = if nch == 2 { f.st[g] } else { NO_STEREO };
+            }
+        }
+    }
+
+    fn quant_of(p: &ParsedMpa) -> Option<&[i16]> {
+        p.fused.as_ref().map(|f| f.quant.as_slice())
+    }
+
+    fn requant_of(p: &ParsedMpa) -> Option<&[ffi::SymaccelMp3Requant]> {
+        p.fused.as_ref().map(|f| f.rq.as_slice())
+    }
+
+    fn side_of(p: &ParsedMpa) -> Option<&[ffi::SymaccelMp3Side]> {
+        Some(p.side.as_slice())
+    }
 }
 
 impl BatchCodec for MpaBatch {
@@ -311,32 +364,18 @@ impl BatchCodec for MpaBatch {
 
     fn transform(&mut self, batch: &[ParsedMpa]) -> Result<()> {
         // (a batch that came through the batcher is done with: this one is published from `pcm`)
-        if let (Some(pool), Some(old)) = (self.pool.clone(), self.cur.take()) {
-            pool.release(old);
-        }
-        self.first_granule.clear();
-        self.trims.clear();
-        let mut total = 0usize;
-        for p in batch {
-            self.first_granule.push(total);
-            self.trims.push(p.trim);
-            total += p.n_granules;
-        }
-        self.first_granule.push(total);
+        self.slots.start_direct(Self::index_of(batch));
+        let first = &self.slots.index().first_granule;
+        let (nch, total) = (self.nch, first[batch.len()]);
+        Self::place(&mut self.side, batch, first, nch, 1, Self::side_of);
         // (every packet of a batch comes from the same front end: all fused, or none)
         if batch.iter().all(|p| p.fused.is_some()) && !batch.is_empty() {
-            return self.transform_fused(batch, total);
+            Self::place(self.quant.as_mut_slice(), batch, first, nch, 576, Self::quant_of);
+            Self::place(&mut self.rq, batch, first, nch, 1, Self::requant_of);
+            Self::place_stereo(&mut self.st, batch, first, nch);
+            return self.transform_fused(total);
         }
-        for (i, p) in batch.iter().enumerate() {
-            for g in 0..p.n_granules {
-                for c in 0..self.nch {
-                    let dst = c * total + self.first_granule[i] + g;
-                    let src = (g * self.nch + c) * 576;
-                    self.xr.as_mut_slice()[dst * 576..(dst + 1) * 576].copy_from_slice(&p.xr[src..src + 576]);
-                    self.side[dst] = p.side[g * self.nch + c];
-                }
-            }
-        }
+        Self::place(self.xr.as_mut_slice(), batch, first, nch, 576, |p| Some(p.xr.as_slice()));
         // SAFETY: every buffer covers nch * total (* 576) elements (sized for max_batch frames of two granules); the
         // call returns after the PCM and the updated state are back in host memory.
         check(
@@ -359,16 +398,14 @@ impl BatchCodec for MpaBatch {
     }
 
     fn publish(&mut self, i: usize) {
-        let total = *self.first_granule.last().unwrap_or(&0);
-        let (g0, g1) = (self.first_granule[i], self.first_granule[i + 1]);
+        let ix = self.slots.index();
+        let total = *ix.first_granule.last().unwrap_or(&0);
+        let (g0, g1) = (ix.first_granule[i], ix.first_granule[i + 1]);
         let frames = (g1 - g0) * 576;
         self.buf.clear();
         self.buf.render_uninit(Some(frames));
         // the batch's PCM: in the batcher's slot (zero-copy: the device wrote it there), or in this decoder's own buffer
-        let pcm: &[f32] = match &self.cur {
-            Some(slot) => slot.out::<f32>(),
-            None => self.pcm.as_slice(),
-        };
+        let pcm: &[f32] = self.slots.out::<f32>().unwrap_or(self.pcm.as_slice());
         for c in 0..self.nch {
             let src = (c * total + g0) * 576;
             if let Some(plane) = self.buf.plane_mut(c) {
@@ -377,7 +414,7 @@ impl BatchCodec for MpaBatch {
         }
         if self.gapless {
             // decoder.rs:128-131
-            self.buf.trim(self.trims[i].0, self.trims[i].1);
+            self.buf.trim(ix.trims[i].0, ix.trims[i].1);
         }
     }
 
@@ -395,155 +432,53 @@ impl BatchCodec for MpaBatch {
     }
 
     fn pooled(&self) -> bool {
-        self.pool.is_some()
+        self.slots.pooled()
     }
 
     /// The stream's next batch goes to the process-wide batcher (one stream = one submission of 1 or 2 chains): the Huffman samples and
-    /// the side records are written straight into a page-locked slot (`Pool::reserve` -> fill -> `commit`); requantize, stereo and the
-    /// synthesis tail run in one launch with the other streams' batches (layer3/mod.rs:421-477).
+    /// the side records are written straight into a page-locked slot; requantize, stereo and the synthesis tail run in one launch with
+    /// the other streams' batches (layer3/mod.rs:421-477).
     fn submit(&mut self, batch: &[ParsedMpa]) -> Result<()> {
-        let Some(pool) = self.pool.clone() else {
-            return unsupported_error("mp3: no batcher");
-        };
-        if batch.is_empty() || !batch.iter().all(|p| p.fused.is_some()) || self.next.is_some() {
-            return unsupported_error("mp3: the batcher takes the entropy decoder's integers, one batch at a time");
+        if batch.is_empty() || !batch.iter().all(|p| p.fused.is_some()) {
+            return unsupported_error("mp3: the batcher takes the entropy decoder's integers");
         }
-        self.next_first_granule.clear();
-        self.next_trims.clear();
-        let mut total = 0usize;
-        for p in batch {
-            self.next_first_granule.push(total);
-            self.next_trims.push(p.trim);
-            total += p.n_granules;
-        }
-        self.next_first_granule.push(total);
-        let nch = self.nch;
-        let mut slot = pool.reserve(ffi::SYMACCEL_BATCH_MP3_DECODE as i32, self.front.sample_rate_idx(), nch, total)?;
-        {
-            // [channel][granule of the batch][576] Huffman samples
-            let quant = slot.input::<i16>(0);
-            for (i, p) in batch.iter().enumerate() {
-                let Some(f) = &p.fused else { continue };
-                for g in 0..p.n_granules {
-                    for c in 0..nch {
-                        let dst = (c * total + self.next_first_granule[i] + g) * 576;
-                        let src = (g * nch + c) * 576;
-                        quant[dst..dst + 576].copy_from_slice(&f.quant[src..src + 576]);
-                    }
-                }
-            }
-        }
-        {
-            let rq = slot.input::<ffi::SymaccelMp3Requant>(1);
-            for (i, p) in batch.iter().enumerate() {
-                let Some(f) = &p.fused else { continue };
-                for g in 0..p.n_granules {
-                    for c in 0..nch {
-                        rq[c * total + self.next_first_granule[i] + g] = f.rq[g * nch + c];
-                    }
-                }
-            }
-        }
-        {
-            let side = slot.input::<ffi::SymaccelMp3Side>(2);
-            for (i, p) in batch.iter().enumerate() {
-                for g in 0..p.n_granules {
-                    for c in 0..nch {
-                        side[c * total + self.next_first_granule[i] + g] = p.side[g * nch + c];
-                    }
-                }
-            }
-        }
-        {
-            // one joint-stereo record per granule of the STREAM (all zeros for a mono stream)
-            let zero_st = ffi::SymaccelMp3Stereo { flags: 0, block_type: 0, is_mixed: 0, reserved: 0, rzero0: 0, rzero1: 0, scalefacs1: [0; 39], pad: 0 };
-            let st = slot.input::<ffi::SymaccelMp3Stereo>(3);
-            for (i, p) in batch.iter().enumerate() {
-                let Some(f) = &p.fused else { continue };
-                for g in 0..p.n_granules {
-                    st[self.next_first_granule[i] + g] = if nch == 2 { f.st[g] } else { zero_st };
-                }
-            }
-        }
-        slot.state::<f32>(0).copy_from_slice(&self.overlap);
-        slot.state::<f32>(1).copy_from_slice(&self.vvec);
-        slot.state::<i32>(2).copy_from_slice(&self.vfront);
-        if let Err(e) = pool.commit(&mut slot) {
-            pool.release(slot);
-            return Err(e);
-        }
-        self.next = Some(slot);
-        Ok(())
+        let index = Self::index_of(batch);
+        let first = index.first_granule.clone();
+        let (nch, total) = (self.nch, first[batch.len()]);
+        self.slots.submit(ffi::SYMACCEL_BATCH_MP3_DECODE as i32, self.front.sample_rate_idx(), nch, total, index, |slot| {
+            Self::place(slot.input::<i16>(0), batch, &first, nch, 576, Self::quant_of);
+            Self::place(slot.input::<ffi::SymaccelMp3Requant>(1), batch, &first, nch, 1, Self::requant_of);
+            Self::place(slot.input::<ffi::SymaccelMp3Side>(2), batch, &first, nch, 1, Self::side_of);
+            Self::place_stereo(slot.input::<ffi::SymaccelMp3Stereo>(3), batch, &first, nch);
+            slot.state::<f32>(0).copy_from_slice(&self.overlap);
+            slot.state::<f32>(1).copy_from_slice(&self.vvec);
+            slot.state::<i32>(2).copy_from_slice(&self.vfront);
+            Ok(())
+        })
     }
 
     fn collect(&mut self) -> Result<()> {
-        let (Some(pool), Some(mut slot)) = (self.pool.clone(), self.next.take()) else {
-            return unsupported_error("mp3: nothing was submitted");
-        };
-        if let Err(e) = pool.wait(&mut slot) {
-            pool.release(slot);
-            return Err(e);
-        }
         // the state after the batch; the PCM stays where it is
-        self.overlap.copy_from_slice(slot.state::<f32>(0));
-        self.vvec.copy_from_slice(slot.state::<f32>(1));
-        self.vfront.copy_from_slice(slot.state::<i32>(2));
-        if let Some(old) = self.cur.take() {
-            pool.release(old);
-        }
-        self.cur = Some(slot);
-        std::mem::swap(&mut self.first_granule, &mut self.next_first_granule);
-        std::mem::swap(&mut self.trims, &mut self.next_trims);
-        Ok(())
+        self.slots.collect(|slot| {
+            self.overlap.copy_from_slice(slot.state::<f32>(0));
+            self.vvec.copy_from_slice(slot.state::<f32>(1));
+            self.vfront.copy_from_slice(slot.state::<i32>(2));
+        })
     }
 
     fn hint(&mut self) {
-        if let Some(pool) = &self.pool {
-            pool.hint();
-        }
+        self.slots.hint();
     }
 
     fn abandon(&mut self) {
-        if let (Some(pool), Some(slot)) = (self.pool.clone(), self.next.take()) {
-            pool.release(slot);
-        }
-    }
-}
-
-impl Drop for MpaBatch {
-    fn drop(&mut self) {
-        BatchCodec::abandon(self);
-        if let (Some(pool), Some(slot)) = (self.pool.clone(), self.cur.take()) {
-            pool.release(slot);
-        }
+        self.slots.abandon();
     }
 }
 
 impl MpaBatch {
     /// layer3/mod.rs:421-477 for the whole batch in one call: requantize, stereo and the synthesis tail on the device from the
-    /// entropy decoder's integers (2 bytes per line in, 4 bytes per sample out).
-    /// The fused batch in the chain-major staging layout (`first`: index of every packet's first granule).
-    fn gather_fused(&mut self, batch: &[ParsedMpa], total: usize, first: &[usize]) {
-        let zero_st = ffi::SymaccelMp3Stereo { flags: 0, block_type: 0, is_mixed: 0, reserved: 0, rzero0: 0, rzero1: 0, scalefacs1: [0; 39], pad: 0 };
-        for (i, p) in batch.iter().enumerate() {
-            let Some(f) = &p.fused else { continue };
-            for g in 0..p.n_granules {
-                let at = first[i] + g;
-                for c in 0..self.nch {
-                    let dst = c * total + at;
-                    let src = (g * self.nch + c) * 576;
-                    self.quant.as_mut_slice()[dst * 576..(dst + 1) * 576].copy_from_slice(&f.quant[src..src + 576]);
-                    self.rq[dst] = f.rq[g * self.nch + c];
-                    self.side[dst] = p.side[g * self.nch + c];
-                }
-                self.st[at] = if self.nch == 2 { f.st[g] } else { zero_st };
-            }
-        }
-    }
-
-    fn transform_fused(&mut self, batch: &[ParsedMpa], total: usize) -> Result<()> {
-        let first = self.first_granule.clone();
-        self.gather_fused(batch, total, &first);
+    /// entropy decoder's integers (2 bytes per line in, 4 bytes per sample out), already placed by `transform`.
+    fn transform_fused(&mut self, total: usize) -> Result<()> {
         let pair: [i32; 2] = [0, 1];
         let n_pairs = if self.nch == 2 { 1 } else { 0 };
         // SAFETY: every buffer covers nch * total (* 576) elements and st covers `total` records (sized for max_batch frames of
@@ -584,22 +519,12 @@ crate::hip_decoder!(
     HipMpaDecoder,
     MpaBatch,
     ParsedMpa,
-    crate::frontends::mpa_front_end,
     &[support_audio_codec!(CODEC_ID_MP3, "mp3", "MPEG Audio Layer 3 (MI355X synthesis)")],
     "MP3 decoder with the same observable behaviour as `symphonia_bundle_mp3::MpaDecoder` for Layer III streams."
 );
+crate::hip_decoder!(@new HipMpaDecoder, crate::frontends::mpa_front_end, Box<dyn MpaFrontEnd>);
 
 impl HipMpaDecoder {
-    pub fn try_new(params: &AudioCodecParameters, opts: &AudioDecoderOptions, front: Box<dyn MpaFrontEnd>, max_batch: usize) -> Result<Self> {
-        Self::try_new_with_pool(params, opts, front, max_batch, None)
-    }
-
-    /// The same decoder submitting to the process-wide cross-stream batcher (`Pool::shared()`): with many streams open, the
-    /// batches of all of them go to the device in one launch (csrc/batcher.cpp).
-    pub fn try_new_pooled(params: &AudioCodecParameters, opts: &AudioDecoderOptions, front: Box<dyn MpaFrontEnd>, max_batch: usize) -> Result<Self> {
-        Self::try_new_with_pool(params, opts, front, max_batch, Some(Pool::shared()?))
-    }
-
     pub fn try_new_with_pool(
         params: &AudioCodecParameters,
         opts: &AudioDecoderOptions,
@@ -630,14 +555,8 @@ impl HipMpaDecoder {
                     ffi::SymaccelMp3Requant { global_gain: 0, flags: 0, block_type: 0, is_mixed: 0, subblock_gain: [0; 3], reserved: 0, rzero: 0, scalefacs: [0; 39], pad: [0; 3] };
                     nch * granules
                 ],
-                st: vec![ffi::SymaccelMp3Stereo { flags: 0, block_type: 0, is_mixed: 0, reserved: 0, rzero0: 0, rzero1: 0, scalefacs1: [0; 39], pad: 0 }; granules],
-                first_granule: Vec::with_capacity(max_batch + 1),
-                trims: Vec::with_capacity(max_batch),
-                pool,
-                cur: None,
-                next: None,
-                next_first_granule: Vec::with_capacity(max_batch + 1),
-                next_trims: Vec::with_capacity(max_batch),
+                st: vec![NO_STEREO; granules],
+                slots: SlotCycle::new(pool, MpaBatch::index_of(&[])),
                 gapless: opts.gapless,
                 buf: AudioBuffer::new(AudioSpec::new(rate, channels), 1152),
             },

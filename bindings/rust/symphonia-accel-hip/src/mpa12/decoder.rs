@@ -4,8 +4,9 @@
 //! and layer checks, allocation, scale factors and sample reads are the reference's code and fail with the reference's errors -- and keeps
 //! what crossed the seam: 16-bit codes and one record per channel.  A packet that fails records nothing, so it contributes no unit, leaves
 //! the state untouched and fails alone when its turn comes (decoder.rs:85-135).  `transform` / `submit` hand a whole look-ahead batch to
-//! `symaccel_mpa12_decode` or to the cross-stream batcher (`SYMACCEL_BATCH_MPA12_DECODE`: a chain is a channel); `publish` copies a
-//! packet's planes out and applies the gapless trim (decoder.rs:128-131); `reset` zeroes the filterbank state (decoder.rs:152-155).
+//! `symaccel_mpa12_decode` or to the cross-stream batcher (`SYMACCEL_BATCH_MPA12_DECODE`: a chain is a channel; its slots through
+//! `SlotCycle`, ctx.rs); `publish` copies a packet's planes out and applies the gapless trim (decoder.rs:128-131); `reset` zeroes the
+//! filterbank state (decoder.rs:152-155).
 //! `register` enters the decoder at `Tier::Preferred`; shapes the device path does not take go to the decoder below (`fallback.rs`).
 use std::sync::{Arc, Mutex};
 
@@ -13,14 +14,13 @@ use symphonia_bundle_mp3::backend::{SubbandBackend, SubbandFrame};
 use symphonia_bundle_mp3::MpaDecoder;
 use symphonia_core::audio::{Audio, AudioBuffer, AudioMut, AudioSpec, GenericAudioBufferRef};
 use symphonia_core::codecs::audio::well_known::{CODEC_ID_MP1, CODEC_ID_MP2};
-use symphonia_core::codecs::audio::{AudioCodecParameters, AudioDecoder, AudioDecoderOptions, FinalizeResult};
-use symphonia_core::codecs::registry::{CodecRegistry, RegisterableAudioDecoder, SupportedAudioCodec};
-use symphonia_core::codecs::CodecInfo;
+use symphonia_core::codecs::audio::{AudioCodecParameters, AudioDecoder, AudioDecoderOptions};
+use symphonia_core::codecs::registry::CodecRegistry;
 use symphonia_core::errors::{decode_error, unsupported_error, Result};
 use symphonia_core::packet::PacketRef;
 use symphonia_core::support_audio_codec;
 
-use crate::ctx::{check, BatchSlot, Context, Pool};
+use crate::ctx::{check, Context, Pool, SlotCycle};
 use crate::decoder::DecoderBatch;
 use crate::ffi;
 use crate::lookahead::{BatchCodec, Lookahead};
@@ -78,13 +78,9 @@ pub struct Mpa12Batch {
     vfront: Vec<i32>,  // [channel]
     pcm: Vec<f32>,     // [channel][packet of the batch][32 * n_frames]
     status: Vec<u8>,   // [channel][packet of the batch]
-    trims: Vec<(usize, usize)>,
-    // the cross-stream batcher: `cur` holds the batch being handed out (its PCM is read in the page-locked slot), `next` the one
-    // submitted ahead (its state lands in `vvec` / `vfront` at collect)
-    pool: Option<Arc<Pool>>,
-    cur: Option<BatchSlot>,
-    next: Option<BatchSlot>,
-    next_trims: Vec<(usize, usize)>,
+    // the cross-stream batcher (ctx.rs, `SlotCycle`); the index of a batch is its packets' trims.  The PCM of a batch that came through
+    // the batcher is read in its page-locked slot, its state lands in `vvec` / `vfront` at collect
+    slots: SlotCycle<Vec<(usize, usize)>>,
     gapless: bool,
     buf: AudioBuffer<f32>,
 }
@@ -92,6 +88,16 @@ pub struct Mpa12Batch {
 impl Mpa12Batch {
     fn packet_samples(&self) -> usize {
         32 * self.layer.n_frames()
+    }
+
+    /// One input plane of a batch, for `symaccel_mpa12_decode` and for the batcher alike: row `c * k + i` = channel `c` of packet `i`.
+    fn place<T: Copy>(rows: &mut [T], batch: &[ParsedMpa12], nch: usize, n: usize, plane: impl Fn(&ParsedMpa12) -> &[T]) {
+        let k = batch.len();
+        for (i, p) in batch.iter().enumerate() {
+            for c in 0..nch {
+                rows[(c * k + i) * n..(c * k + i + 1) * n].copy_from_slice(&plane(p)[c * n..(c + 1) * n]);
+            }
+        }
     }
 }
 
@@ -116,22 +122,14 @@ impl BatchCodec for Mpa12Batch {
     }
 
     fn transform(&mut self, batch: &[ParsedMpa12]) -> Result<()> {
-        if let (Some(pool), Some(old)) = (self.pool.clone(), self.cur.take()) {
-            pool.release(old);
-        }
+        self.slots.start_direct(batch.iter().map(|p| p.trim).collect());
         let (k, n, rb, nch) = (batch.len(), self.packet_samples(), self.layer.record_bytes(), self.nch);
-        self.trims.clear();
         self.codes.clear();
         self.codes.resize(nch * k * n, 0u16);
         self.rec.clear();
         self.rec.resize(nch * k * rb, 0u8);
-        for (i, p) in batch.iter().enumerate() {
-            self.trims.push(p.trim);
-            for c in 0..nch {
-                self.codes[(c * k + i) * n..(c * k + i + 1) * n].copy_from_slice(&p.codes[c * n..(c + 1) * n]);
-                self.rec[(c * k + i) * rb..(c * k + i + 1) * rb].copy_from_slice(&p.rec[c * rb..(c + 1) * rb]);
-            }
-        }
+        Self::place(&mut self.codes, batch, nch, n, |p| p.codes.as_slice());
+        Self::place(&mut self.rec, batch, nch, rb, |p| p.rec.as_slice());
         self.pcm.clear();
         self.pcm.resize(nch * k * n, 0.0f32);
         self.status.clear();
@@ -148,13 +146,12 @@ impl BatchCodec for Mpa12Batch {
     }
 
     fn publish(&mut self, i: usize) {
-        let (k, n) = (self.trims.len(), self.packet_samples());
+        let n = self.packet_samples();
+        let trims = self.slots.index();
+        let k = trims.len();
         self.buf.clear();
         self.buf.render_uninit(Some(n));
-        let pcm: &[f32] = match &self.cur {
-            Some(slot) => slot.out::<f32>(),
-            None => self.pcm.as_slice(),
-        };
+        let pcm: &[f32] = self.slots.out::<f32>().unwrap_or(self.pcm.as_slice());
         for c in 0..self.nch {
             let src = (c * k + i) * n;
             if let Some(plane) = self.buf.plane_mut(c) {
@@ -163,7 +160,7 @@ impl BatchCodec for Mpa12Batch {
         }
         if self.gapless {
             // decoder.rs:128-131
-            self.buf.trim(self.trims[i].0, self.trims[i].1);
+            self.buf.trim(trims[i].0, trims[i].1);
         }
     }
 
@@ -179,86 +176,38 @@ impl BatchCodec for Mpa12Batch {
     }
 
     fn pooled(&self) -> bool {
-        self.pool.is_some()
+        self.slots.pooled()
     }
 
     fn submit(&mut self, batch: &[ParsedMpa12]) -> Result<()> {
-        let Some(pool) = self.pool.clone() else {
-            return unsupported_error("mpa: no batcher");
-        };
-        if batch.is_empty() || self.next.is_some() {
-            return unsupported_error("mpa: one batch of at least one packet at a time");
+        if batch.is_empty() {
+            return unsupported_error("mpa: a batch of at least one packet");
         }
         let (k, n, rb, nch) = (batch.len(), self.packet_samples(), self.layer.record_bytes(), self.nch);
-        let mut slot = pool.reserve(ffi::SYMACCEL_BATCH_MPA12_DECODE as i32, self.layer.raw(), nch, k)?;
-        self.next_trims.clear();
-        for p in batch {
-            self.next_trims.push(p.trim);
-        }
-        {
-            let codes = slot.input::<u16>(0);
-            for (i, p) in batch.iter().enumerate() {
-                for c in 0..nch {
-                    codes[(c * k + i) * n..(c * k + i + 1) * n].copy_from_slice(&p.codes[c * n..(c + 1) * n]);
-                }
-            }
-        }
-        {
-            let rec = slot.input::<u8>(1);
-            for (i, p) in batch.iter().enumerate() {
-                for c in 0..nch {
-                    rec[(c * k + i) * rb..(c * k + i + 1) * rb].copy_from_slice(&p.rec[c * rb..(c + 1) * rb]);
-                }
-            }
-        }
-        slot.state::<f32>(0).copy_from_slice(&self.vvec);
-        slot.state::<i32>(1).copy_from_slice(&self.vfront);
-        if let Err(e) = pool.commit(&mut slot) {
-            pool.release(slot);
-            return Err(e);
-        }
-        self.next = Some(slot);
-        Ok(())
+        let trims: Vec<(usize, usize)> = batch.iter().map(|p| p.trim).collect();
+        self.slots.submit(ffi::SYMACCEL_BATCH_MPA12_DECODE as i32, self.layer.raw(), nch, k, trims, |slot| {
+            Self::place(slot.input::<u16>(0), batch, nch, n, |p| p.codes.as_slice());
+            Self::place(slot.input::<u8>(1), batch, nch, rb, |p| p.rec.as_slice());
+            slot.state::<f32>(0).copy_from_slice(&self.vvec);
+            slot.state::<i32>(1).copy_from_slice(&self.vfront);
+            Ok(())
+        })
     }
 
     fn collect(&mut self) -> Result<()> {
-        let (Some(pool), Some(mut slot)) = (self.pool.clone(), self.next.take()) else {
-            return unsupported_error("mpa: nothing was submitted");
-        };
-        if let Err(e) = pool.wait(&mut slot) {
-            pool.release(slot);
-            return Err(e);
-        }
         // the state after the batch; the PCM stays where it is
-        self.vvec.copy_from_slice(slot.state::<f32>(0));
-        self.vfront.copy_from_slice(slot.state::<i32>(1));
-        if let Some(old) = self.cur.take() {
-            pool.release(old);
-        }
-        self.cur = Some(slot);
-        std::mem::swap(&mut self.trims, &mut self.next_trims);
-        Ok(())
+        self.slots.collect(|slot| {
+            self.vvec.copy_from_slice(slot.state::<f32>(0));
+            self.vfront.copy_from_slice(slot.state::<i32>(1));
+        })
     }
 
     fn hint(&mut self) {
-        if let Some(pool) = &self.pool {
-            pool.hint();
-        }
+        self.slots.hint();
     }
 
     fn abandon(&mut self) {
-        if let (Some(pool), Some(slot)) = (self.pool.clone(), self.next.take()) {
-            pool.release(slot);
-        }
-    }
-}
-
-impl Drop for Mpa12Batch {
-    fn drop(&mut self) {
-        BatchCodec::abandon(self);
-        if let (Some(pool), Some(slot)) = (self.pool.clone(), self.cur.take()) {
-            pool.release(slot);
-        }
+        self.slots.abandon();
     }
 }
 
@@ -268,23 +217,19 @@ impl DecoderBatch for Mpa12Batch {
     }
 }
 
-/// Layer I / Layer II decoder with the same observable behaviour as `symphonia_bundle_mp3::MpaDecoder`.
-pub struct HipMpa12Decoder {
-    params: AudioCodecParameters,
-    batch: Mpa12Batch,
-    la: Lookahead<ParsedMpa12>,
-}
+crate::hip_decoder!(
+    HipMpa12Decoder,
+    Mpa12Batch,
+    ParsedMpa12,
+    &[
+        support_audio_codec!(CODEC_ID_MP1, "mp1", "MPEG Audio Layer 1 (MI355X)"),
+        support_audio_codec!(CODEC_ID_MP2, "mp2", "MPEG Audio Layer 2 (MI355X)"),
+    ],
+    "Layer I / Layer II decoder with the same observable behaviour as `symphonia_bundle_mp3::MpaDecoder`."
+);
+crate::hip_decoder!(@new HipMpa12Decoder);
 
 impl HipMpa12Decoder {
-    pub fn try_new(params: &AudioCodecParameters, opts: &AudioDecoderOptions, max_batch: usize) -> Result<Self> {
-        Self::try_new_with_pool(params, opts, max_batch, None)
-    }
-
-    /// The same decoder submitting to the process-wide cross-stream batcher (`Pool::shared()`).
-    pub fn try_new_pooled(params: &AudioCodecParameters, opts: &AudioDecoderOptions, max_batch: usize) -> Result<Self> {
-        Self::try_new_with_pool(params, opts, max_batch, Some(Pool::shared()?))
-    }
-
     pub fn try_new_with_pool(params: &AudioCodecParameters, opts: &AudioDecoderOptions, max_batch: usize, pool: Option<Arc<Pool>>) -> Result<Self> {
         let layer = if params.codec == CODEC_ID_MP1 {
             MpaLayer::Layer1
@@ -322,69 +267,12 @@ impl HipMpa12Decoder {
                 vfront: vec![0; nch],
                 pcm: Vec::new(),
                 status: Vec::new(),
-                trims: Vec::with_capacity(max_batch),
-                pool,
-                cur: None,
-                next: None,
-                next_trims: Vec::with_capacity(max_batch),
+                slots: SlotCycle::new(pool, Vec::new()),
                 gapless: opts.gapless,
                 buf: AudioBuffer::new(AudioSpec::new(rate, channels), 1152),
             },
             la: Lookahead::new(max_batch),
         })
-    }
-}
-
-impl AudioDecoder for HipMpa12Decoder {
-    /// decoder.rs:152-155: what was computed ahead is dropped and the state is zeroed.
-    fn reset(&mut self) {
-        self.la.reset_with(&mut self.batch);
-        BatchCodec::reset_state(&mut self.batch);
-    }
-
-    fn codec_info(&self) -> &CodecInfo {
-        // the codec that is in use (decoder.rs:139-146)
-        &Self::supported_codecs().iter().find(|desc| desc.id == self.params.codec).expect("codec registered in supported_codecs").info
-    }
-
-    fn codec_params(&self) -> &AudioCodecParameters {
-        &self.params
-    }
-
-    fn decode_ref(&mut self, packet: &PacketRef<'_>) -> Result<GenericAudioBufferRef<'_>> {
-        // (Lookahead::decode clears the buffer on every error path: decoder.rs:157-161)
-        self.la.decode(&mut self.batch, packet)?;
-        Ok(DecoderBatch::buffer(&self.batch))
-    }
-
-    fn finalize(&mut self) -> FinalizeResult {
-        Default::default()
-    }
-
-    fn last_decoded(&self) -> GenericAudioBufferRef<'_> {
-        DecoderBatch::buffer(&self.batch)
-    }
-}
-
-impl RegisterableAudioDecoder for HipMpa12Decoder {
-    fn try_registry_new(params: &AudioCodecParameters, opts: &AudioDecoderOptions) -> Result<Box<dyn AudioDecoder>> {
-        // as the other decoders of this crate: on the shared batcher if there is one; a shape, a device or memory this decoder cannot
-        // have sends the track to the decoder that was registered below
-        let built = match Pool::shared() {
-            Ok(pool) => Self::try_new_with_pool(params, opts, crate::DEFAULT_LOOKAHEAD, Some(pool)),
-            Err(_) => Self::try_new(params, opts, crate::DEFAULT_LOOKAHEAD),
-        };
-        match built {
-            Ok(decoder) => Ok(Box::new(decoder)),
-            Err(e) => crate::fallback::make(params, opts, e),
-        }
-    }
-
-    fn supported_codecs() -> &'static [SupportedAudioCodec] {
-        &[
-            support_audio_codec!(CODEC_ID_MP1, "mp1", "MPEG Audio Layer 1 (MI355X)"),
-            support_audio_codec!(CODEC_ID_MP2, "mp2", "MPEG Audio Layer 2 (MI355X)"),
-        ]
     }
 }
 

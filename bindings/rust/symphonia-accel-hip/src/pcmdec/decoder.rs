@@ -2,9 +2,9 @@
 //! `PcmDecoder::try_new` (lib.rs:220-316) in their order with their error variants, then refuses what the device decoder leaves to the
 //! decoder below (more than 8 channels, a coded width of 0); `parse` counts a packet's whole frames (lib.rs:320: a trailing partial frame
 //! is dropped, an empty packet is 0 frames, no packet fails); `transform` / `submit` hand a whole look-ahead batch to
-//! `symaccel_pcm_decode` or to the cross-stream batcher (`SYMACCEL_BATCH_PCM_DECODE`: a chain is a packet) as ONE call: every packet is a
-//! row of `units` frames, the frames of the batch's longest packet, a shorter one followed by zero bytes -- streams cut their packets to
-//! one size, so the batches of every stream of one shape meet in the same launches; `publish` copies a packet's planes into a
+//! `symaccel_pcm_decode` or to the cross-stream batcher (`SYMACCEL_BATCH_PCM_DECODE`: a chain is a packet; its slots through
+//! `SlotCycle`, ctx.rs) as ONE call: every packet is a row of `units` frames, the frames of the batch's longest packet, a shorter one
+//! followed by zero bytes -- streams cut their packets to one size, so the batches of every stream of one shape meet in the same launches; `publish` copies a packet's planes into a
 //! `GenericAudioBuffer` of the reference's variant (lib.rs:248-262).  `register` enters the decoder at `Tier::Preferred` for the twenty
 //! ids.  No seam patch and no `frontends.rs` entry are needed: there is no host front end.
 use std::sync::Arc;
@@ -16,14 +16,13 @@ use symphonia_core::codecs::audio::well_known::{
     CODEC_ID_PCM_S16LE, CODEC_ID_PCM_S24BE, CODEC_ID_PCM_S24LE, CODEC_ID_PCM_S32BE, CODEC_ID_PCM_S32LE, CODEC_ID_PCM_S8, CODEC_ID_PCM_U16BE,
     CODEC_ID_PCM_U16LE, CODEC_ID_PCM_U24BE, CODEC_ID_PCM_U24LE, CODEC_ID_PCM_U32BE, CODEC_ID_PCM_U32LE, CODEC_ID_PCM_U8,
 };
-use symphonia_core::codecs::audio::{AudioCodecParameters, AudioDecoder, AudioDecoderOptions, FinalizeResult};
-use symphonia_core::codecs::registry::{CodecRegistry, RegisterableAudioDecoder, SupportedAudioCodec};
-use symphonia_core::codecs::CodecInfo;
+use symphonia_core::codecs::audio::{AudioCodecParameters, AudioDecoderOptions};
+use symphonia_core::codecs::registry::CodecRegistry;
 use symphonia_core::errors::{decode_error, unsupported_error, Result};
 use symphonia_core::packet::PacketRef;
 use symphonia_core::support_audio_codec;
 
-use crate::ctx::{check, BatchSlot, Context, Pool};
+use crate::ctx::{check, Context, Pool, SlotCycle};
 use crate::decoder::DecoderBatch;
 use crate::ffi;
 use crate::lookahead::{BatchCodec, Lookahead};
@@ -125,14 +124,15 @@ pub struct PcmBatch {
     shape: PcmShape,
     rows: Vec<u8>,       // the packets of the current batch, `units` frames each, zero bytes behind a shorter one
     pcm: Vec<u8>,        // [packet][channel][units] native samples
-    units: usize,        // frames every packet of the current batch occupies
-    frames: Vec<usize>,  // frames of each packet of the batch
-    pool: Option<Arc<Pool>>,
-    cur: Option<BatchSlot>,
-    next: Option<BatchSlot>,
-    next_units: usize,
-    next_frames: Vec<usize>,
+    // the cross-stream batcher through the slot cycle of ctx.rs: the PCM of a batch that came through it is read in its page-locked slot
+    slots: SlotCycle<PcmIndex>,
     buf: GenericAudioBuffer,
+}
+
+/// Where `publish` finds a packet in its batch.
+pub struct PcmIndex {
+    units: usize,        // frames every packet of the batch occupies
+    frames: Vec<usize>,  // frames of each packet of the batch
 }
 
 /// plane[f] of every channel of `$buf` from the native bytes of packet `$i`
@@ -157,14 +157,9 @@ impl PcmBatch {
         self.shape.codec.raw() | ((self.shape.channels as i32) << 8) | ((self.shape.shift as i32) << 16)
     }
 
-    fn units_of(batch: &[ParsedPcm]) -> usize {
-        let mut units = 0;
-        for p in batch {
-            if p.frames > units {
-                units = p.frames;
-            }
-        }
-        units
+    /// `units`: the frames of the batch's longest packet.
+    fn index_of(batch: &[ParsedPcm]) -> PcmIndex {
+        PcmIndex { units: batch.iter().map(|p| p.frames).max().unwrap_or(0), frames: batch.iter().map(|p| p.frames).collect() }
     }
 
     fn place(rows: &mut [u8], batch: &[ParsedPcm], pitch: usize) {
@@ -190,16 +185,10 @@ impl BatchCodec for PcmBatch {
     }
 
     fn transform(&mut self, batch: &[ParsedPcm]) -> Result<()> {
-        if let (Some(pool), Some(old)) = (self.pool.clone(), self.cur.take()) {
-            pool.release(old);
-        }
         let (nch, fb) = (self.shape.channels, self.shape.coded_bytes * self.shape.channels);
-        let units = Self::units_of(batch);
-        self.units = units;
-        self.frames.clear();
-        for p in batch {
-            self.frames.push(p.frames);
-        }
+        let index = Self::index_of(batch);
+        let units = index.units;
+        self.slots.start_direct(index);
         self.rows.clear();
         self.rows.resize(batch.len() * units * fb, 0u8);
         Self::place(&mut self.rows, batch, units * fb);
@@ -217,11 +206,9 @@ impl BatchCodec for PcmBatch {
     }
 
     fn publish(&mut self, i: usize) {
-        let (nch, nb, units, frames) = (self.shape.channels, self.shape.native_bytes, self.units, self.frames[i]);
-        let pcm: &[u8] = match &self.cur {
-            Some(slot) => slot.out::<u8>(),
-            None => self.pcm.as_slice(),
-        };
+        let ix = self.slots.index();
+        let (nch, nb, units, frames) = (self.shape.channels, self.shape.native_bytes, ix.units, ix.frames[i]);
+        let pcm: &[u8] = self.slots.out::<u8>().unwrap_or(self.pcm.as_slice());
         match &mut self.buf {
             GenericAudioBuffer::U8(buf) => pcm_fill!(buf, pcm, i, nch, units, frames, nb, |b: &[u8]| b[0]),
             GenericAudioBuffer::U16(buf) => pcm_fill!(buf, pcm, i, nch, units, frames, nb, |b: &[u8]| u16::from_ne_bytes([b[0], b[1]])),
@@ -246,69 +233,32 @@ impl BatchCodec for PcmBatch {
     }
 
     fn pooled(&self) -> bool {
-        self.pool.is_some()
+        self.slots.pooled()
     }
 
     fn submit(&mut self, batch: &[ParsedPcm]) -> Result<()> {
-        let Some(pool) = self.pool.clone() else {
-            return unsupported_error("pcm: no batcher");
-        };
-        if batch.is_empty() || self.next.is_some() {
-            return unsupported_error("pcm: one batch of at least one packet at a time");
+        if batch.is_empty() {
+            return unsupported_error("pcm: a batch of at least one packet");
         }
         let fb = self.shape.coded_bytes * self.shape.channels;
-        let units = Self::units_of(batch);
-        let mut slot = pool.reserve(ffi::SYMACCEL_BATCH_PCM_DECODE as i32, self.param(), batch.len(), units)?;
-        Self::place(slot.input::<u8>(0), batch, units * fb);
-        self.next_units = units;
-        self.next_frames.clear();
-        for p in batch {
-            self.next_frames.push(p.frames);
-        }
-        if let Err(e) = pool.commit(&mut slot) {
-            pool.release(slot);
-            return Err(e);
-        }
-        self.next = Some(slot);
-        Ok(())
+        let index = Self::index_of(batch);
+        let (param, units) = (self.param(), index.units);
+        self.slots.submit(ffi::SYMACCEL_BATCH_PCM_DECODE as i32, param, batch.len(), units, index, |slot| {
+            Self::place(slot.input::<u8>(0), batch, units * fb);
+            Ok(())
+        })
     }
 
     fn collect(&mut self) -> Result<()> {
-        let (Some(pool), Some(mut slot)) = (self.pool.clone(), self.next.take()) else {
-            return unsupported_error("pcm: nothing was submitted");
-        };
-        if let Err(e) = pool.wait(&mut slot) {
-            pool.release(slot);
-            return Err(e);
-        }
-        if let Some(old) = self.cur.take() {
-            pool.release(old);
-        }
-        self.cur = Some(slot);
-        self.units = self.next_units;
-        std::mem::swap(&mut self.frames, &mut self.next_frames);
-        Ok(())
+        self.slots.collect(|_| {})
     }
 
     fn hint(&mut self) {
-        if let Some(pool) = &self.pool {
-            pool.hint();
-        }
+        self.slots.hint();
     }
 
     fn abandon(&mut self) {
-        if let (Some(pool), Some(slot)) = (self.pool.clone(), self.next.take()) {
-            pool.release(slot);
-        }
-    }
-}
-
-impl Drop for PcmBatch {
-    fn drop(&mut self) {
-        BatchCodec::abandon(self);
-        if let (Some(pool), Some(slot)) = (self.pool.clone(), self.cur.take()) {
-            pool.release(slot);
-        }
+        self.slots.abandon();
     }
 }
 
@@ -318,116 +268,47 @@ impl DecoderBatch for PcmBatch {
     }
 }
 
-/// PCM decoder with the same observable behaviour as `symphonia_codec_pcm::PcmDecoder`.
-pub struct HipPcmDecoder {
-    params: AudioCodecParameters,
-    batch: PcmBatch,
-    la: Lookahead<ParsedPcm>,
-}
+crate::hip_decoder!(
+    HipPcmDecoder,
+    PcmBatch,
+    ParsedPcm,
+    // the same twenty descriptors as lib.rs:448-560, by id
+    &[
+        support_audio_codec!(CODEC_ID_PCM_S32LE, "pcm_s32le", "PCM Signed 32-bit Little-Endian Interleaved (MI355X)"),
+        support_audio_codec!(CODEC_ID_PCM_S32BE, "pcm_s32be", "PCM Signed 32-bit Big-Endian Interleaved (MI355X)"),
+        support_audio_codec!(CODEC_ID_PCM_S24LE, "pcm_s24le", "PCM Signed 24-bit Little-Endian Interleaved (MI355X)"),
+        support_audio_codec!(CODEC_ID_PCM_S24BE, "pcm_s24be", "PCM Signed 24-bit Big-Endian Interleaved (MI355X)"),
+        support_audio_codec!(CODEC_ID_PCM_S16LE, "pcm_s16le", "PCM Signed 16-bit Little-Endian Interleaved (MI355X)"),
+        support_audio_codec!(CODEC_ID_PCM_S16BE, "pcm_s16be", "PCM Signed 16-bit Big-Endian Interleaved (MI355X)"),
+        support_audio_codec!(CODEC_ID_PCM_S8, "pcm_s8", "PCM Signed 8-bit Interleaved (MI355X)"),
+        support_audio_codec!(CODEC_ID_PCM_U32LE, "pcm_u32le", "PCM Unsigned 32-bit Little-Endian Interleaved (MI355X)"),
+        support_audio_codec!(CODEC_ID_PCM_U32BE, "pcm_u32be", "PCM Unsigned 32-bit Big-Endian Interleaved (MI355X)"),
+        support_audio_codec!(CODEC_ID_PCM_U24LE, "pcm_u24le", "PCM Unsigned 24-bit Little-Endian Interleaved (MI355X)"),
+        support_audio_codec!(CODEC_ID_PCM_U24BE, "pcm_u24be", "PCM Unsigned 24-bit Big-Endian Interleaved (MI355X)"),
+        support_audio_codec!(CODEC_ID_PCM_U16LE, "pcm_u16le", "PCM Unsigned 16-bit Little-Endian Interleaved (MI355X)"),
+        support_audio_codec!(CODEC_ID_PCM_U16BE, "pcm_u16be", "PCM Unsigned 16-bit Big-Endian Interleaved (MI355X)"),
+        support_audio_codec!(CODEC_ID_PCM_U8, "pcm_u8", "PCM Unsigned 8-bit Interleaved (MI355X)"),
+        support_audio_codec!(CODEC_ID_PCM_F32LE, "pcm_f32le", "PCM 32-bit Little-Endian Floating Point Interleaved (MI355X)"),
+        support_audio_codec!(CODEC_ID_PCM_F32BE, "pcm_f32be", "PCM 32-bit Big-Endian Floating Point Interleaved (MI355X)"),
+        support_audio_codec!(CODEC_ID_PCM_F64LE, "pcm_f64le", "PCM 64-bit Little-Endian Floating Point Interleaved (MI355X)"),
+        support_audio_codec!(CODEC_ID_PCM_F64BE, "pcm_f64be", "PCM 64-bit Big-Endian Floating Point Interleaved (MI355X)"),
+        support_audio_codec!(CODEC_ID_PCM_ALAW, "pcm_alaw", "PCM A-law (MI355X)"),
+        support_audio_codec!(CODEC_ID_PCM_MULAW, "pcm_mulaw", "PCM Mu-law (MI355X)"),
+    ],
+    "PCM decoder with the same observable behaviour as `symphonia_codec_pcm::PcmDecoder`."
+);
+crate::hip_decoder!(@new HipPcmDecoder);
 
 impl HipPcmDecoder {
-    pub fn try_new(params: &AudioCodecParameters, opts: &AudioDecoderOptions, max_batch: usize) -> Result<Self> {
-        Self::try_new_with_pool(params, opts, max_batch, None)
-    }
-
-    /// The same decoder submitting to the process-wide cross-stream batcher (`Pool::shared()`).
-    pub fn try_new_pooled(params: &AudioCodecParameters, opts: &AudioDecoderOptions, max_batch: usize) -> Result<Self> {
-        Self::try_new_with_pool(params, opts, max_batch, Some(Pool::shared()?))
-    }
-
     pub fn try_new_with_pool(params: &AudioCodecParameters, opts: &AudioDecoderOptions, max_batch: usize, pool: Option<Arc<Pool>>) -> Result<Self> {
         let shape = pcm_shape(params, opts)?;
         // lib.rs:313: a buffer of the codec's sample format
         let buf = GenericAudioBuffer::new(shape.format, AudioSpec::new(shape.rate, shape.layout.clone()), shape.capacity);
         Ok(HipPcmDecoder {
             params: params.clone(),
-            batch: PcmBatch {
-                ctx: Context::new(0)?,
-                shape,
-                rows: Vec::new(),
-                pcm: Vec::new(),
-                units: 0,
-                frames: Vec::new(),
-                pool,
-                cur: None,
-                next: None,
-                next_units: 0,
-                next_frames: Vec::new(),
-                buf,
-            },
+            batch: PcmBatch { ctx: Context::new(0)?, shape, rows: Vec::new(), pcm: Vec::new(), slots: SlotCycle::new(pool, PcmBatch::index_of(&[])), buf },
             la: Lookahead::new(max_batch.max(1)),
         })
-    }
-}
-
-impl AudioDecoder for HipPcmDecoder {
-    /// Nothing is carried between packets (lib.rs:415-417): only what was computed ahead is dropped.
-    fn reset(&mut self) {
-        self.la.reset_with(&mut self.batch);
-        BatchCodec::reset_state(&mut self.batch);
-    }
-
-    fn codec_info(&self) -> &CodecInfo {
-        // the codec that is in use (lib.rs:419-426)
-        &Self::supported_codecs().iter().find(|desc| desc.id == self.params.codec).expect("codec registered in supported_codecs").info
-    }
-
-    fn codec_params(&self) -> &AudioCodecParameters {
-        &self.params
-    }
-
-    fn decode_ref(&mut self, packet: &PacketRef<'_>) -> Result<GenericAudioBufferRef<'_>> {
-        self.la.decode(&mut self.batch, packet)?;
-        Ok(DecoderBatch::buffer(&self.batch))
-    }
-
-    fn finalize(&mut self) -> FinalizeResult {
-        Default::default()
-    }
-
-    fn last_decoded(&self) -> GenericAudioBufferRef<'_> {
-        DecoderBatch::buffer(&self.batch)
-    }
-}
-
-impl RegisterableAudioDecoder for HipPcmDecoder {
-    fn try_registry_new(params: &AudioCodecParameters, opts: &AudioDecoderOptions) -> Result<Box<dyn AudioDecoder>> {
-        // as the other decoders of this crate (decoder.rs): on the shared batcher if there is one; a shape, a device or memory this
-        // decoder cannot have sends the track to the decoder that was registered below
-        let built = match Pool::shared() {
-            Ok(pool) => Self::try_new_with_pool(params, opts, crate::DEFAULT_LOOKAHEAD, Some(pool)),
-            Err(_) => Self::try_new(params, opts, crate::DEFAULT_LOOKAHEAD),
-        };
-        match built {
-            Ok(decoder) => Ok(Box::new(decoder)),
-            Err(e) => crate::fallback::make(params, opts, e),
-        }
-    }
-
-    fn supported_codecs() -> &'static [SupportedAudioCodec] {
-        // the same twenty descriptors as lib.rs:448-560, by id
-        &[
-            support_audio_codec!(CODEC_ID_PCM_S32LE, "pcm_s32le", "PCM Signed 32-bit Little-Endian Interleaved (MI355X)"),
-            support_audio_codec!(CODEC_ID_PCM_S32BE, "pcm_s32be", "PCM Signed 32-bit Big-Endian Interleaved (MI355X)"),
-            support_audio_codec!(CODEC_ID_PCM_S24LE, "pcm_s24le", "PCM Signed 24-bit Little-Endian Interleaved (MI355X)"),
-            support_audio_codec!(CODEC_ID_PCM_S24BE, "pcm_s24be", "PCM Signed 24-bit Big-Endian Interleaved (MI355X)"),
-            support_audio_codec!(CODEC_ID_PCM_S16LE, "pcm_s16le", "PCM Signed 16-bit Little-Endian Interleaved (MI355X)"),
-            support_audio_codec!(CODEC_ID_PCM_S16BE, "pcm_s16be", "PCM Signed 16-bit Big-Endian Interleaved (MI355X)"),
-            support_audio_codec!(CODEC_ID_PCM_S8, "pcm_s8", "PCM Signed 8-bit Interleaved (MI355X)"),
-            support_audio_codec!(CODEC_ID_PCM_U32LE, "pcm_u32le", "PCM Unsigned 32-bit Little-Endian Interleaved (MI355X)"),
-            support_audio_codec!(CODEC_ID_PCM_U32BE, "pcm_u32be", "PCM Unsigned 32-bit Big-Endian Interleaved (MI355X)"),
-            support_audio_codec!(CODEC_ID_PCM_U24LE, "pcm_u24le", "PCM Unsigned 24-bit Little-Endian Interleaved (MI355X)"),
-            support_audio_codec!(CODEC_ID_PCM_U24BE, "pcm_u24be", "PCM Unsigned 24-bit Big-Endian Interleaved (MI355X)"),
-            support_audio_codec!(CODEC_ID_PCM_U16LE, "pcm_u16le", "PCM Unsigned 16-bit Little-Endian Interleaved (MI355X)"),
-            support_audio_codec!(CODEC_ID_PCM_U16BE, "pcm_u16be", "PCM Unsigned 16-bit Big-Endian Interleaved (MI355X)"),
-            support_audio_codec!(CODEC_ID_PCM_U8, "pcm_u8", "PCM Unsigned 8-bit Interleaved (MI355X)"),
-            support_audio_codec!(CODEC_ID_PCM_F32LE, "pcm_f32le", "PCM 32-bit Little-Endian Floating Point Interleaved (MI355X)"),
-            support_audio_codec!(CODEC_ID_PCM_F32BE, "pcm_f32be", "PCM 32-bit Big-Endian Floating Point Interleaved (MI355X)"),
-            support_audio_codec!(CODEC_ID_PCM_F64LE, "pcm_f64le", "PCM 64-bit Little-Endian Floating Point Interleaved (MI355X)"),
-            support_audio_codec!(CODEC_ID_PCM_F64BE, "pcm_f64be", "PCM 64-bit Big-Endian Floating Point Interleaved (MI355X)"),
-            support_audio_codec!(CODEC_ID_PCM_ALAW, "pcm_alaw", "PCM A-law (MI355X)"),
-            support_audio_codec!(CODEC_ID_PCM_MULAW, "pcm_mulaw", "PCM Mu-law (MI355X)"),
-        ]
     }
 }
 

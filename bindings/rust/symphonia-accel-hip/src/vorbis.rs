@@ -14,7 +14,7 @@ use symphonia_core::errors::{decode_error, unsupported_error, Result};
 use symphonia_core::packet::PacketRef;
 use symphonia_core::support_audio_codec;
 
-use crate::ctx::{check, BatchSlot, Context, Pinned, Pool};
+use crate::ctx::{check, Context, Pinned, Pool, SlotCycle};
 use crate::decoder::DecoderBatch;
 use crate::ffi;
 use crate::lookahead::{BatchCodec, Lookahead};
@@ -229,27 +229,110 @@ pub struct VorbisBatch {
     prev_flag: Vec<i32>,      // [channel]: -1 = no previous block (after reset), else the last block's flag
     overlap: Vec<f32>,        // [channel][bs1 / 2]
     pcm: Pinned<f32>,         // [channel][packed samples of the batch]
-    spec_stride: usize,
-    pcm_stride: usize,
-    pcm_off: Vec<usize>,      // per packet of the batch: offset of its samples in a channel's PCM; one extra = total
-    emits: Vec<bool>,         // per packet: false for the first block after a reset (lib.rs:335-338: silenced when gapless)
-    trims: Vec<(usize, usize)>, // per packet of the batch
     floors: Vec<ffi::SymaccelVorbisFloor1Cfg>, // the fused form: the stream's floor-1 configurations,
     floor: Vec<u8>,           //   [channel][packet] floor index or SYMACCEL_VORBIS_FLOOR_UNUSED,
     posts: Vec<u32>,          //   [channel][packet][POSTS]
     // the cross-stream batcher (SYMACCEL_BATCH_VORBIS_DECODE for a front end that hands on residue + posts, SYMACCEL_BATCH_VORBIS_SYNTH for
-    // one that hands on spectra): every chain's planes at their largest -- max_batch x bs1 / 2 --, the packed data at the front, so that
-    // streams with different block flags share a launch.  `cur` holds the batch being handed out (its PCM is read where the device left
-    // it), `next` the one submitted ahead; `floor_index` = what the batcher calls this stream's floor configurations.
-    pool: Option<Arc<Pool>>,
-    cur: Option<BatchSlot>,
-    next: Option<BatchSlot>,
+    // one that hands on spectra) through the slot cycle of ctx.rs: every chain's planes at their largest -- max_batch x bs1 / 2 --, the
+    // packed data at the front, so that streams with different block flags share a launch.  The PCM of a batch that came through it is
+    // read where the device left it; `floor_index` = what the batcher calls this stream's floor configurations.
+    slots: SlotCycle<VorbisIndex>,
     floor_index: Vec<u8>,
-    next_pcm_off: Vec<usize>,
-    next_emits: Vec<bool>,
-    next_trims: Vec<(usize, usize)>,
-    next_stride: usize,
     buf: AudioBuffer<f32>,
+}
+
+/// Where `publish` finds a packet in its batch.
+pub struct VorbisIndex {
+    pcm_stride: usize,           // samples of a channel's PCM plane (direct: the packed samples of the batch; through the batcher: the plane at its largest)
+    pcm_off: Vec<usize>,         // per packet of the batch: offset of its samples in a channel's PCM; one extra = total
+    emits: Vec<bool>,            // per packet: false for the first block after a reset (lib.rs:335-338: silenced when gapless)
+    trims: Vec<(usize, usize)>,  // per packet of the batch
+}
+
+/// The writers below give a batch the ONE layout `symaccel_vorbis_decode` / `symaccel_vorbis_synth` and the batcher's slot share, into
+/// whichever planes they are handed.  Two things remain apart on purpose: the pitch of a chain's spectrum plane (the packed lines of the
+/// batch in this decoder's own buffer, the plane at its largest in the slot -- a parameter of `place_spectra`), and the coupling steps
+/// (two host arrays for the direct call, one blob plane in the slot: `coupling_of` makes the arrays, the blob is written in `submit`).
+impl VorbisBatch {
+    /// The packed layout of a batch inside a chain (include/symaccel.h, "Vorbis"): block b owns n_b / 2 lines and (prev_n + n_b) / 4
+    /// samples; a first block without a previous one owns n_b / 2 sample slots and leaves them untouched.  Returns the offset of every
+    /// packet's lines, the lines of the batch, and the index (`pcm_stride` = the samples of the batch).
+    fn pack(bs: &[usize; 2], prev_flag: i32, batch: &[ParsedVorbis]) -> (Vec<usize>, usize, VorbisIndex) {
+        let mut prev = prev_flag;
+        let (mut lines, mut samples) = (0usize, 0usize);
+        let mut spec_off = Vec::with_capacity(batch.len());
+        let mut index = VorbisIndex { pcm_stride: 0, pcm_off: Vec::with_capacity(batch.len() + 1), emits: Vec::with_capacity(batch.len()), trims: Vec::with_capacity(batch.len()) };
+        for p in batch {
+            let n = bs[p.long_block as usize];
+            spec_off.push(lines);
+            index.pcm_off.push(samples);
+            index.emits.push(prev >= 0);
+            index.trims.push(p.trim);
+            lines += n / 2;
+            samples += if prev >= 0 { (bs[prev as usize] + n) / 4 } else { n / 2 };
+            prev = p.long_block as i32;
+        }
+        index.pcm_off.push(samples);
+        index.pcm_stride = samples;
+        (spec_off, lines, index)
+    }
+
+    /// [channel][packed lines]: a chain's plane is `pitch` lines
+    fn place_spectra(dst: &mut [f32], batch: &[ParsedVorbis], bs: &[usize; 2], nch: usize, pitch: usize, spec_off: &[usize]) {
+        for (i, p) in batch.iter().enumerate() {
+            let half = bs[p.long_block as usize] / 2;
+            for c in 0..nch {
+                let at = c * pitch + spec_off[i];
+                dst[at..at + half].copy_from_slice(&p.spectra[c * half..(c + 1) * half]);
+            }
+        }
+    }
+
+    /// [channel][packet]
+    fn place_flags(dst: &mut [u8], batch: &[ParsedVorbis], nch: usize) {
+        let k = batch.len();
+        for (i, p) in batch.iter().enumerate() {
+            for c in 0..nch {
+                dst[c * k + i] = p.long_block as u8;
+            }
+        }
+    }
+
+    /// [channel][packet]: the floor of every channel-block under the number `name` gives the stream's own
+    fn place_floor(dst: &mut [u8], batch: &[ParsedVorbis], nch: usize, name: impl Fn(u8) -> u8) {
+        let k = batch.len();
+        for (i, p) in batch.iter().enumerate() {
+            let Some(f) = &p.fused else { continue };
+            for c in 0..nch {
+                dst[c * k + i] = name(f.floor[c]);
+            }
+        }
+    }
+
+    /// [channel][packet][POSTS]
+    fn place_posts(dst: &mut [u32], batch: &[ParsedVorbis], nch: usize) {
+        let k = batch.len();
+        for (i, p) in batch.iter().enumerate() {
+            let Some(f) = &p.fused else { continue };
+            for c in 0..nch {
+                let at = (c * k + i) * POSTS;
+                dst[at..at + POSTS].copy_from_slice(&f.posts[c * POSTS..(c + 1) * POSTS]);
+            }
+        }
+    }
+
+    /// The (magnitude, angle) pairs of the batch back to back, and the index of every packet's first step; one extra = total.
+    fn coupling_of(batch: &[ParsedVorbis]) -> (Vec<u8>, Vec<u32>) {
+        let mut steps: Vec<u8> = Vec::new();
+        let mut first: Vec<u32> = Vec::with_capacity(batch.len() + 1);
+        first.push(0);
+        for p in batch {
+            let Some(f) = &p.fused else { continue };
+            steps.extend_from_slice(&f.coupling);
+            first.push((steps.len() / 2) as u32);
+        }
+        (steps, first)
+    }
 }
 
 impl BatchCodec for VorbisBatch {
@@ -260,40 +343,13 @@ impl BatchCodec for VorbisBatch {
     }
 
     fn transform(&mut self, batch: &[ParsedVorbis]) -> Result<()> {
+        let (k, nch) = (batch.len(), self.nch);
+        let (spec_off, lines, index) = Self::pack(&self.bs, self.prev_flag[0], batch);
+        let samples = index.pcm_stride;
         // (a batch that came through the batcher is done with: this one is published from `pcm`)
-        if let (Some(pool), Some(old)) = (self.pool.clone(), self.cur.take()) {
-            pool.release(old);
-        }
-        let k = batch.len();
-        // the packed layout of include/symaccel.h ("Vorbis"): block b owns n_b / 2 lines and (prev_n + n_b) / 4 samples;
-        // a first block without a previous one owns n_b / 2 sample slots and leaves them untouched
-        let mut prev: i32 = self.prev_flag[0];
-        let (mut lines, mut samples) = (0usize, 0usize);
-        let mut spec_off = Vec::with_capacity(k);
-        self.pcm_off.clear();
-        self.emits.clear();
-        self.trims.clear();
-        for p in batch {
-            self.trims.push(p.trim);
-            let n = self.bs[p.long_block as usize];
-            spec_off.push(lines);
-            self.pcm_off.push(samples);
-            self.emits.push(prev >= 0);
-            lines += n / 2;
-            samples += if prev >= 0 { (self.bs[prev as usize] + n) / 4 } else { n / 2 };
-            prev = p.long_block as i32;
-        }
-        self.pcm_off.push(samples);
-        self.spec_stride = lines;
-        self.pcm_stride = samples;
-        for (i, p) in batch.iter().enumerate() {
-            let half = self.bs[p.long_block as usize] / 2;
-            for c in 0..self.nch {
-                let dst = c * lines + spec_off[i];
-                self.spectra.as_mut_slice()[dst..dst + half].copy_from_slice(&p.spectra[c * half..(c + 1) * half]);
-                self.flags[c * k + i] = p.long_block as u8;
-            }
-        }
+        self.slots.start_direct(index);
+        Self::place_spectra(self.spectra.as_mut_slice(), batch, &self.bs, nch, lines, &spec_off);
+        Self::place_flags(&mut self.flags, batch, nch);
         let (bs0_exp, bs1_exp) = self.front.block_exps();
         if k > 0 && batch.iter().all(|p| p.fused.is_some()) {
             return self.transform_fused(batch, lines, samples);
@@ -321,23 +377,21 @@ impl BatchCodec for VorbisBatch {
     }
 
     fn publish(&mut self, i: usize) {
-        let frames = if self.emits[i] { self.pcm_off[i + 1] - self.pcm_off[i] } else { 0 };
+        let ix = self.slots.index();
+        let frames = if ix.emits[i] { ix.pcm_off[i + 1] - ix.pcm_off[i] } else { 0 };
         self.buf.clear();
         self.buf.render_uninit(Some(frames));
         // the batch's PCM: in the batcher's slot (zero-copy: the device wrote it there), or in this decoder's own buffer
-        let pcm: &[f32] = match &self.cur {
-            Some(slot) => slot.out::<f32>(),
-            None => self.pcm.as_slice(),
-        };
+        let pcm: &[f32] = self.slots.out::<f32>().unwrap_or(self.pcm.as_slice());
         for c in 0..self.nch {
-            let src = c * self.pcm_stride + self.pcm_off[i];
+            let src = c * ix.pcm_stride + ix.pcm_off[i];
             if let Some(plane) = self.buf.plane_mut(c) {
                 plane[..frames].copy_from_slice(&pcm[src..src + frames]);
             }
         }
         // lib.rs:333-342 (gapless): the first packet after a reset is silenced (`emits`), every other one is trimmed
-        if self.emits[i] {
-            self.buf.trim(self.trims[i].0, self.trims[i].1);
+        if ix.emits[i] {
+            self.buf.trim(ix.trims[i].0, ix.trims[i].1);
         }
     }
 
@@ -353,18 +407,15 @@ impl BatchCodec for VorbisBatch {
     }
 
     fn pooled(&self) -> bool {
-        self.pool.is_some()
+        self.slots.pooled()
     }
 
     /// The stream's next batch goes to the process-wide batcher: residue (or spectra), flags, floor indices, posts and the coupling steps
     /// are written straight into a page-locked slot; coupling, floor curves, dot product and synthesis run in one launch with the other
     /// streams' batches (lib.rs:250-331).
     fn submit(&mut self, batch: &[ParsedVorbis]) -> Result<()> {
-        let Some(pool) = self.pool.clone() else {
-            return unsupported_error("vorbis: no batcher");
-        };
-        if batch.is_empty() || self.next.is_some() {
-            return unsupported_error("vorbis: one batch at a time");
+        if batch.is_empty() {
+            return unsupported_error("vorbis: an empty batch");
         }
         let (k, nch) = (batch.len(), self.nch);
         let fused = batch.iter().all(|p| p.fused.is_some());
@@ -373,83 +424,28 @@ impl BatchCodec for VorbisBatch {
         }
         let (bs0_exp, bs1_exp) = self.front.block_exps();
         let cap = k * self.bs[1] / 2; // a chain's spectrum / PCM plane at its largest
-        // the packed layout of the batch inside a chain (as `transform`)
-        let mut prev: i32 = self.prev_flag[0];
-        let (mut lines, mut samples) = (0usize, 0usize);
-        let mut spec_off = Vec::with_capacity(k);
-        self.next_pcm_off.clear();
-        self.next_emits.clear();
-        self.next_trims.clear();
-        for p in batch {
-            let n = self.bs[p.long_block as usize];
-            spec_off.push(lines);
-            self.next_pcm_off.push(samples);
-            self.next_emits.push(prev >= 0);
-            self.next_trims.push(p.trim);
-            lines += n / 2;
-            samples += if prev >= 0 { (self.bs[prev as usize] + n) / 4 } else { n / 2 };
-            prev = p.long_block as i32;
-        }
-        self.next_pcm_off.push(samples);
-        self.next_stride = cap;
+        let (spec_off, _, mut index) = Self::pack(&self.bs, self.prev_flag[0], batch);
+        index.pcm_stride = cap;
         let (kind, param) = if fused {
             (ffi::SYMACCEL_BATCH_VORBIS_DECODE as i32, bs0_exp | (bs1_exp << 8) | ((nch as i32) << 16))
         }
         else {
             (ffi::SYMACCEL_BATCH_VORBIS_SYNTH as i32, bs0_exp | (bs1_exp << 8))
         };
-        let mut slot = pool.reserve(kind, param, nch, k)?;
-        {
-            let spectra = slot.input::<f32>(0);
-            for (i, p) in batch.iter().enumerate() {
-                let half = self.bs[p.long_block as usize] / 2;
-                for c in 0..nch {
-                    let dst = c * cap + spec_off[i];
-                    spectra[dst..dst + half].copy_from_slice(&p.spectra[c * half..(c + 1) * half]);
-                }
-            }
-        }
-        {
-            let flags = slot.input::<u8>(1);
-            for (i, p) in batch.iter().enumerate() {
-                for c in 0..nch {
-                    flags[c * k + i] = p.long_block as u8;
-                }
-            }
-        }
-        if fused {
-            let mut steps: Vec<u8> = Vec::new();
-            let mut first: Vec<u32> = Vec::with_capacity(k + 1);
-            first.push(0);
-            {
-                let floor = slot.input::<u8>(2);
-                for (i, p) in batch.iter().enumerate() {
-                    let Some(f) = &p.fused else { continue };
-                    for c in 0..nch {
-                        // (the stream's floor numbers become the batcher's: registered when the decoder was built)
-                        let local = f.floor[c] as usize;
-                        floor[c * k + i] = if local < self.floor_index.len() { self.floor_index[local] } else { ffi::SYMACCEL_VORBIS_FLOOR_UNUSED as u8 };
-                    }
-                    steps.extend_from_slice(&f.coupling);
-                    first.push((steps.len() / 2) as u32);
-                }
-            }
-            {
-                let posts = slot.input::<u32>(3);
-                for (i, p) in batch.iter().enumerate() {
-                    let Some(f) = &p.fused else { continue };
-                    for c in 0..nch {
-                        let dst = (c * k + i) * POSTS;
-                        posts[dst..dst + POSTS].copy_from_slice(&f.posts[c * POSTS..(c + 1) * POSTS]);
-                    }
-                }
-            }
-            {
+        self.slots.submit(kind, param, nch, k, index, |slot| {
+            Self::place_spectra(slot.input::<f32>(0), batch, &self.bs, nch, cap, &spec_off);
+            Self::place_flags(slot.input::<u8>(1), batch, nch);
+            if fused {
+                // (the stream's floor numbers become the batcher's: registered when the decoder was built)
+                Self::place_floor(slot.input::<u8>(2), batch, nch, |local| {
+                    if (local as usize) < self.floor_index.len() { self.floor_index[local as usize] } else { ffi::SYMACCEL_VORBIS_FLOOR_UNUSED as u8 }
+                });
+                Self::place_posts(slot.input::<u32>(3), batch, nch);
                 // the coupling blob: first[k + 1] u32 (little endian), padded to 16 bytes, then the (magnitude, angle) pairs
+                let (steps, first) = Self::coupling_of(batch);
                 let blob = slot.input::<u8>(4);
                 let steps_at = ((k + 1) * 4 + 15) & !15;
                 if steps_at + steps.len() > blob.len() {
-                    pool.release(slot);
                     return unsupported_error("vorbis: more coupling steps than a batcher submission holds");
                 }
                 for (b, v) in first.iter().enumerate() {
@@ -457,58 +453,26 @@ impl BatchCodec for VorbisBatch {
                 }
                 blob[steps_at..steps_at + steps.len()].copy_from_slice(&steps);
             }
-        }
-        slot.state::<i32>(0).copy_from_slice(&self.prev_flag);
-        slot.state::<f32>(1).copy_from_slice(&self.overlap);
-        if let Err(e) = pool.commit(&mut slot) {
-            pool.release(slot);
-            return Err(e);
-        }
-        self.next = Some(slot);
-        Ok(())
+            slot.state::<i32>(0).copy_from_slice(&self.prev_flag);
+            slot.state::<f32>(1).copy_from_slice(&self.overlap);
+            Ok(())
+        })
     }
 
     fn collect(&mut self) -> Result<()> {
-        let (Some(pool), Some(mut slot)) = (self.pool.clone(), self.next.take()) else {
-            return unsupported_error("vorbis: nothing was submitted");
-        };
-        if let Err(e) = pool.wait(&mut slot) {
-            pool.release(slot);
-            return Err(e);
-        }
         // the lapping state after the batch; the PCM stays where it is
-        self.prev_flag.copy_from_slice(slot.state::<i32>(0));
-        self.overlap.copy_from_slice(slot.state::<f32>(1));
-        if let Some(old) = self.cur.take() {
-            pool.release(old);
-        }
-        self.cur = Some(slot);
-        self.pcm_stride = self.next_stride;
-        std::mem::swap(&mut self.pcm_off, &mut self.next_pcm_off);
-        std::mem::swap(&mut self.emits, &mut self.next_emits);
-        std::mem::swap(&mut self.trims, &mut self.next_trims);
-        Ok(())
+        self.slots.collect(|slot| {
+            self.prev_flag.copy_from_slice(slot.state::<i32>(0));
+            self.overlap.copy_from_slice(slot.state::<f32>(1));
+        })
     }
 
     fn hint(&mut self) {
-        if let Some(pool) = &self.pool {
-            pool.hint();
-        }
+        self.slots.hint();
     }
 
     fn abandon(&mut self) {
-        if let (Some(pool), Some(slot)) = (self.pool.clone(), self.next.take()) {
-            pool.release(slot);
-        }
-    }
-}
-
-impl Drop for VorbisBatch {
-    fn drop(&mut self) {
-        BatchCodec::abandon(self);
-        if let (Some(pool), Some(slot)) = (self.pool.clone(), self.cur.take()) {
-            pool.release(slot);
-        }
+        self.slots.abandon();
     }
 }
 
@@ -517,19 +481,9 @@ impl VorbisBatch {
     /// the packet decoder's residue vectors (already packed into `spectra` by `transform`) and posts.
     fn transform_fused(&mut self, batch: &[ParsedVorbis], lines: usize, samples: usize) -> Result<()> {
         let k = batch.len();
-        let mut coupling: Vec<u8> = Vec::new();
-        let mut first: Vec<u32> = Vec::with_capacity(k + 1);
-        first.push(0);
-        for (i, p) in batch.iter().enumerate() {
-            let Some(f) = &p.fused else { continue };
-            for c in 0..self.nch {
-                self.floor[c * k + i] = f.floor[c];
-                let dst = (c * k + i) * POSTS;
-                self.posts[dst..dst + POSTS].copy_from_slice(&f.posts[c * POSTS..(c + 1) * POSTS]);
-            }
-            coupling.extend_from_slice(&f.coupling);
-            first.push((coupling.len() / 2) as u32);
-        }
+        Self::place_floor(&mut self.floor, batch, self.nch, |local| local);
+        Self::place_posts(&mut self.posts, batch, self.nch);
+        let (coupling, first) = Self::coupling_of(batch);
         let (bs0_exp, bs1_exp) = self.front.block_exps();
         // SAFETY: residue / flags / floor / posts / pcm cover nch chains of `lines` / k / k / k * POSTS / `samples` elements (sized for
         // max_batch long blocks), `first` k + 1 entries, `coupling` two bytes per step; null stands for an empty step list.  The
@@ -574,22 +528,12 @@ crate::hip_decoder!(
     HipVorbisDecoder,
     VorbisBatch,
     ParsedVorbis,
-    crate::frontends::vorbis_front_end,
     &[support_audio_codec!(CODEC_ID_VORBIS, "vorbis", "Vorbis (MI355X synthesis)")],
     "Vorbis decoder with the same observable behaviour as `symphonia_codec_vorbis::VorbisDecoder`."
 );
+crate::hip_decoder!(@new HipVorbisDecoder, crate::frontends::vorbis_front_end, Box<dyn VorbisFrontEnd>);
 
 impl HipVorbisDecoder {
-    pub fn try_new(params: &AudioCodecParameters, opts: &AudioDecoderOptions, front: Box<dyn VorbisFrontEnd>, max_batch: usize) -> Result<Self> {
-        Self::try_new_with_pool(params, opts, front, max_batch, None)
-    }
-
-    /// The same decoder submitting to the process-wide cross-stream batcher (`Pool::shared()`): the batches of every open Vorbis stream
-    /// with these block sizes and this channel count go to the device in one launch (csrc/batcher.cpp, SYMACCEL_BATCH_VORBIS_DECODE).
-    pub fn try_new_pooled(params: &AudioCodecParameters, opts: &AudioDecoderOptions, front: Box<dyn VorbisFrontEnd>, max_batch: usize) -> Result<Self> {
-        Self::try_new_with_pool(params, opts, front, max_batch, Some(Pool::shared()?))
-    }
-
     pub fn try_new_with_pool(
         params: &AudioCodecParameters,
         opts: &AudioDecoderOptions,
@@ -642,22 +586,11 @@ impl HipVorbisDecoder {
                 prev_flag: vec![-1; nch],
                 overlap: vec![0.0; nch * bs[1] / 2],
                 pcm: Pinned::new(nch * max_batch * bs[1] / 2)?,
-                spec_stride: 0,
-                pcm_stride: 0,
-                pcm_off: Vec::with_capacity(max_batch + 1),
-                emits: Vec::with_capacity(max_batch),
-                trims: Vec::with_capacity(max_batch),
                 floors,
                 floor: vec![0; nch * max_batch],
                 posts: vec![0; nch * max_batch * POSTS],
-                pool,
-                cur: None,
-                next: None,
+                slots: SlotCycle::new(pool, VorbisBatch::pack(&bs, -1, &[]).2),
                 floor_index,
-                next_pcm_off: Vec::with_capacity(max_batch + 1),
-                next_emits: Vec::with_capacity(max_batch),
-                next_trims: Vec::with_capacity(max_batch),
-                next_stride: 0,
                 buf: AudioBuffer::new(AudioSpec::new(rate, channels), bs[1] / 2),
             },
             la: Lookahead::new(max_batch),
