@@ -4,9 +4,9 @@
 //! of the batch into the decoder-owned `AudioBuffer`) that also exposes that buffer; the macro wraps it in a struct
 //! with the trait's observable behaviour: `reset()` zeroes the carried state and drops pre-computed frames
 //! (codecs/audio.rs:252-257), a failed `decode_ref` leaves the buffer cleared (:273-278), `last_decoded()` returns the
-//! buffer of the last successful call (:291-297), `codec_info()` is the descriptor of the codec in use, `finalize()` has
-//! nothing to verify (no decoder in this crate carries a checksum: FLAC's MD5 is computed by the caller over what we return,
-//! as with the reference's decoder when `verify` is off).
+//! buffer of the last successful call (:291-297), `codec_info()` is the descriptor of the codec in use, `finalize()` is the
+//! codec's (`BatchCodec::finalize_result`: FLAC with `verify` answers with the MD5 of STREAMINFO over the packets handed out, the
+//! others have no checksum, like the reference's).
 //!
 //! The macro's `@new` arms write the constructors that only forward -- `try_new` (no batcher), `try_new_pooled` (the process-wide
 //! one) and what `try_registry_new` builds with -- in one of two shapes: `(params, opts, front, max_batch)` for the five decoders
@@ -124,7 +124,7 @@ macro_rules! hip_decoder {
             }
 
             fn finalize(&mut self) -> symphonia_core::codecs::audio::FinalizeResult {
-                Default::default()
+                $crate::lookahead::BatchCodec::finalize_result(&mut self.batch)
             }
 
             fn last_decoded(&self) -> symphonia_core::audio::GenericAudioBufferRef<'_> {

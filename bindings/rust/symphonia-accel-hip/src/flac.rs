@@ -6,7 +6,7 @@ use std::sync::{Arc, Mutex};
 use symphonia_bundle_flac::{Decorrelation, FlacDecoder, SynthBackend};
 use symphonia_core::audio::{Audio, AudioBuffer, AudioMut, AudioSpec, GenericAudioBufferRef};
 use symphonia_core::codecs::audio::well_known::CODEC_ID_FLAC;
-use symphonia_core::codecs::audio::{AudioCodecParameters, AudioDecoder, AudioDecoderOptions};
+use symphonia_core::codecs::audio::{AudioCodecParameters, AudioDecoder, AudioDecoderOptions, FinalizeResult, VerificationCheck};
 use symphonia_core::errors::{decode_error, unsupported_error, Result};
 use symphonia_core::packet::PacketRef;
 use symphonia_core::support_audio_codec;
@@ -35,6 +35,10 @@ pub trait FlacFrontEnd: Send + Sync {
     fn channels(&self) -> usize;
     fn max_blocksize(&self) -> usize;
     fn parse(&mut self, packet: &PacketRef<'_>) -> Result<ParsedFlac>;
+    /// STREAMINFO's MD5 of the decoded audio, if the stream carries one (decoder.rs:118-119): what `finalize()` compares with.
+    fn expected_md5(&self) -> Option<[u8; 16]> {
+        None
+    }
 }
 
 /// What the reference's decoder tells its `SynthBackend` about one frame (bindings/rust/patches/symphonia-bundle-flac.diff):
@@ -137,6 +141,13 @@ impl FlacFrontEnd for SeamFrontEnd {
         self.max_bs
     }
 
+    fn expected_md5(&self) -> Option<[u8; 16]> {
+        match self.dec.codec_params().verification_check {
+            Some(VerificationCheck::Md5(md5)) => Some(md5),
+            _ => None,
+        }
+    }
+
     fn parse(&mut self, packet: &PacketRef<'_>) -> Result<ParsedFlac> {
         self.rec.lock().expect("flac record poisoned").begin_frame(self.nch);
         let planes = match self.dec.decode_ref(packet)? {
@@ -168,6 +179,18 @@ pub struct FlacBatch {
     // restored words of a batch that came through it are read where the device left them, in the page-locked slot
     slots: SlotCycle<FlacIndex>,
     buf: AudioBuffer<i32>,
+    // Verification (`AudioDecoderOptions::verify`: the MD5 of STREAMINFO, validate.rs:25-75).  A batch through the batcher takes the
+    // verify form of the kind (param 0x200 | (nch - 1) << 12: restore, then one MD5 wavefront per stream in the same launch) and comes
+    // back with the state after every frame in the slot's state plane; a batch this decoder transforms itself is hashed by
+    // symaccel_flac_md5 over the restored words.  `published` is the state after the last packet handed out (what `finalize` digests),
+    // `chain_end` the state after the last frame of the most recently computed batch (what the next batch starts from); a seek, a skip
+    // or an error drops the difference -- the reference's reset() leaves its validator alone (decoder.rs:254-256).
+    verify: bool,
+    replaying: bool,
+    expected: Option<[u8; 16]>,
+    published: ffi::SymaccelMd5State,
+    chain_end: ffi::SymaccelMd5State,
+    cps: Vec<ffi::SymaccelMd5State>,  // the state after every packet of a batch transformed here (a slot carries its own)
 }
 
 /// Where `publish` finds a packet in its batch.
@@ -179,6 +202,23 @@ pub struct FlacIndex {
 }
 
 const NO_DESC: ffi::SymaccelFlacDesc = ffi::SymaccelFlacDesc { kind: 0, order: 0, shift: 0, wasted_bits: 0 };
+
+fn md5_initial() -> ffi::SymaccelMd5State {
+    let mut st = ffi::SymaccelMd5State { abcd: [0; 4], len: 0, tail: [0; 64] };
+    // SAFETY: a valid record; host arithmetic.
+    unsafe { ffi::symaccel_md5_init(&mut st) };
+    st
+}
+
+/// What the MD5 kernel needs to know of a frame: its block size, its channel assignment, and its width in bytes --
+/// ceil(bits per sample / 8) (validate.rs:39-45), bits per sample being 32 - out_shift.
+fn md5_frame(p: &ParsedFlac, nch: usize) -> ffi::SymaccelFlacMd5Frame {
+    ffi::SymaccelFlacMd5Frame {
+        block_len: p.blocksize as u16,
+        pair_mode: if nch == 2 { p.pair_mode } else { 0 },
+        bytes_per_sample: ((32 - p.out_shift + 7) / 8) as u8,
+    }
+}
 
 impl FlacBatch {
     fn index_of(batch: &[ParsedFlac], nch: usize, stride: usize) -> FlacIndex {
@@ -218,10 +258,39 @@ impl BatchCodec for FlacBatch {
         check(
             unsafe { ffi::symaccel_flac_restore(self.ctx.raw(), words.as_mut_ptr(), self.desc.as_ptr(), self.coeffs.as_ptr(), k * nch, stride) },
             self.ctx.raw(),
-        )
+        )?;
+        self.cps.clear();
+        if self.verify && !self.replaying && k > 0 {
+            // the restored words, before the decorrelation and the shift: what the reference hashes (decoder.rs:231-234)
+            let frames: Vec<ffi::SymaccelFlacMd5Frame> = batch.iter().map(|p| md5_frame(p, nch)).collect();
+            self.cps.resize(k, self.chain_end);
+            // SAFETY: `words` holds the k * nch rows of `stride` words just restored; `frames` and `cps` have k entries.
+            check(
+                unsafe {
+                    ffi::symaccel_flac_md5(self.ctx.raw(), words.as_ptr(), stride, frames.as_ptr(), k, nch as i32, 0, &mut self.chain_end, self.cps.as_mut_ptr())
+                },
+                self.ctx.raw(),
+            )?;
+        }
+        Ok(())
     }
 
     fn publish(&mut self, i: usize) {
+        if self.verify {
+            // checkpoint i: of the slot the batch came in, or of the batch transformed here
+            let slot_cp = match self.slots.parts_mut() {
+                (_, Some(slot)) => Some(slot.state::<ffi::SymaccelMd5State>(0)[i]),
+                _ => None,
+            };
+            match slot_cp {
+                Some(cp) => self.published = cp,
+                None => {
+                    if i < self.cps.len() {
+                        self.published = self.cps[i];
+                    }
+                }
+            }
+        }
         let ix = self.slots.index();
         let (n, stride, mode, shift) = (ix.lens[i], ix.stride, ix.modes[i], ix.shifts[i]);
         self.buf.clear();
@@ -257,7 +326,27 @@ impl BatchCodec for FlacBatch {
         }
     }
 
-    fn reset_state(&mut self) {}
+    fn reset_state(&mut self) {
+        self.chain_end = self.published;
+    }
+
+    fn rewind(&mut self) {
+        self.chain_end = self.published;
+    }
+
+    fn set_replaying(&mut self, on: bool) {
+        self.replaying = on;
+    }
+
+    fn finalize_result(&mut self) -> FinalizeResult {
+        // (no digest in STREAMINFO: the reference only warns, decoder.rs:302-304)
+        FinalizeResult {
+            verify_ok: match (self.verify, self.expected) {
+                (true, Some(expected)) => Some(self.md5_so_far() == expected),
+                _ => None,
+            },
+        }
+    }
 
     fn clear(&mut self) {
         self.buf.clear();
@@ -275,16 +364,40 @@ impl BatchCodec for FlacBatch {
         }
         let (k, nch) = (batch.len(), self.nch);
         let stride = self.front.max_blocksize(); // (the same for every batch of the stream: the group key)
-        self.slots.submit(ffi::SYMACCEL_BATCH_FLAC_RESTORE as i32, 0, k * nch, stride, Self::index_of(batch, nch, stride), |slot| {
+        // verifying: the kind's verify form -- a frame record per packet and the state the chain starts from, entry 0 of the state plane
+        let (verify, start) = (self.verify, self.chain_end);
+        let param = if verify { 0x200 | ((nch as i32 - 1) << 12) } else { 0 };
+        self.slots.submit(ffi::SYMACCEL_BATCH_FLAC_RESTORE as i32, param, k * nch, stride, Self::index_of(batch, nch, stride), |slot| {
             place_rows(slot.input::<i32>(0), batch, nch, stride, 0, |p| p.words.as_slice());
             place_rows(slot.input::<ffi::SymaccelFlacDesc>(1), batch, nch, 1, NO_DESC, |p| p.desc.as_slice());
             place_rows(slot.input::<i32>(2), batch, nch, 32, 0, |p| p.coeffs.as_slice());
+            if verify {
+                let frames = slot.input::<ffi::SymaccelFlacMd5Frame>(3);
+                for (i, p) in batch.iter().enumerate() {
+                    frames[i] = md5_frame(p, nch);
+                }
+                slot.state::<ffi::SymaccelMd5State>(0)[0] = start;
+            }
             Ok(())
         })
     }
 
     fn collect(&mut self) -> Result<()> {
-        self.slots.collect(|_| {})
+        // (verifying: entry f of the slot's state plane is the state after frame f -- `publish` reads it there)
+        let mut end: Option<ffi::SymaccelMd5State> = None;
+        let verify = self.verify;
+        self.slots.collect(|slot| {
+            if verify {
+                let cps = slot.state::<ffi::SymaccelMd5State>(0);
+                if !cps.is_empty() {
+                    end = Some(cps[cps.len() - 1]);
+                }
+            }
+        })?;
+        if let Some(st) = end {
+            self.chain_end = st;
+        }
+        Ok(())
     }
 
     fn hint(&mut self) {
@@ -293,6 +406,17 @@ impl BatchCodec for FlacBatch {
 
     fn abandon(&mut self) {
         self.slots.abandon();
+        self.chain_end = self.published;
+    }
+}
+
+impl FlacBatch {
+    /// The MD5 over the packets handed out so far (the digest pads a copy: the chain goes on).
+    pub fn md5_so_far(&self) -> [u8; 16] {
+        let mut digest = [0u8; 16];
+        // SAFETY: a valid state, room for the 16 bytes of the digest; host arithmetic.
+        unsafe { ffi::symaccel_md5_digest(&self.published, digest.as_mut_ptr()) };
+        digest
     }
 }
 
@@ -307,7 +431,7 @@ crate::hip_decoder!(
     FlacBatch,
     ParsedFlac,
     &[support_audio_codec!(CODEC_ID_FLAC, "flac", "Free Lossless Audio Codec (MI355X predictors)")],
-    "FLAC decoder with the same observable behaviour as `symphonia_bundle_flac::FlacDecoder` (verification off)."
+    "FLAC decoder with the same observable behaviour as `symphonia_bundle_flac::FlacDecoder`; with `verify` (on the cross-stream batcher) the MD5 of STREAMINFO is computed on the device and `finalize()` answers as the reference's."
 );
 crate::hip_decoder!(@new HipFlacDecoder, crate::frontends::flac_front_end, Box<dyn FlacFrontEnd>);
 
@@ -319,9 +443,13 @@ impl HipFlacDecoder {
         max_batch: usize,
         pool: Option<Arc<Pool>>,
     ) -> Result<Self> {
-        if opts.verify {
-            // the MD5 of STREAMINFO is computed over the decoded audio inside the reference's decoder; here the caller verifies
-            return unsupported_error("flac: verification is not available with the batched predictors");
+        if opts.verify && pool.is_none() {
+            // the MD5 chain (~1 us per 64-byte block per stream) is affordable only behind the batcher, where the MD5 launch of one
+            // group overlaps the copies and the restore of the next on another lane: without a pool the decoder below verifies
+            return unsupported_error("flac: verification needs the cross-stream batcher");
+        }
+        if opts.verify && front.channels() > 8 {
+            return unsupported_error("flac: verification of more than 8 channels");
         }
         let params = front.params().clone();
         let (Some(rate), Some(channels)) = (params.sample_rate, params.channels.clone()) else {
@@ -330,6 +458,7 @@ impl HipFlacDecoder {
         let nch = front.channels();
         let max_batch = max_batch.max(1);
         let max_bs = front.max_blocksize();
+        let expected = if opts.verify { front.expected_md5() } else { None };
         Ok(HipFlacDecoder {
             params,
             batch: FlacBatch {
@@ -341,6 +470,12 @@ impl HipFlacDecoder {
                 coeffs: vec![0; max_batch * nch * 32],
                 slots: SlotCycle::new(pool, FlacBatch::index_of(&[], nch, max_bs)),
                 buf: AudioBuffer::new(AudioSpec::new(rate, channels), max_bs),
+                verify: opts.verify,
+                replaying: false,
+                expected,
+                published: md5_initial(),
+                chain_end: md5_initial(),
+                cps: Vec::new(),
             },
             la: Lookahead::new(max_batch),
         })

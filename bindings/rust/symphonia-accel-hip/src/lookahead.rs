@@ -18,6 +18,7 @@
 use std::collections::{HashMap, VecDeque};
 use std::sync::{Arc, Mutex, Weak};
 
+use symphonia_core::codecs::audio::FinalizeResult;
 use symphonia_core::errors::{unsupported_error, Result};
 use symphonia_core::formats::{Attachment, FormatInfo, FormatReader, MediaInfo, SeekMode, SeekTo, SeekedTo, Track};
 use symphonia_core::io::MediaSourceStream;
@@ -231,6 +232,18 @@ pub trait BatchCodec {
     fn hint(&mut self) {}
     /// Drop the submitted batch unseen (reset, discontinuity): its results are never looked at, the carried state stays.
     fn abandon(&mut self) {}
+
+    // ---- a codec that verifies its stream (FLAC: the MD5 of STREAMINFO).  What counts is what was handed out: `publish` is where a
+    // packet enters the checksum.  The defaults describe a codec without a checksum.
+    /// Whatever was computed beyond the last packet handed out is dropped (reset, skipped packets, an error): the checksum goes on
+    /// from that packet.
+    fn rewind(&mut self) {}
+    /// Around the one-packet replay after a discontinuity: that packet was counted when it was handed out.
+    fn set_replaying(&mut self, _on: bool) {}
+    /// `AudioDecoder::finalize` (codecs/audio.rs:283-290).
+    fn finalize_result(&mut self) -> FinalizeResult {
+        FinalizeResult { verify_ok: None }
+    }
 }
 
 /// The batching state of a decoder: every one of the crate's eight has one (`hip_decoder!`, decoder.rs).
@@ -286,6 +299,7 @@ impl<P> Lookahead<P> {
         if self.next_live {
             codec.abandon();
         }
+        codec.rewind();
         self.next_live = false;
         self.next_parsed.clear();
         self.next_ready.clear();
@@ -308,7 +322,10 @@ impl<P> Lookahead<P> {
             self.drop_next(codec);
             let replay = if self.head >= 1 { Some(self.head - 1) } else { None };
             if let Some(i) = replay {
-                if let Err(e) = codec.transform(&self.parsed[i..i + 1]) {
+                codec.set_replaying(true);
+                let replayed = codec.transform(&self.parsed[i..i + 1]);
+                codec.set_replaying(false);
+                if let Err(e) = replayed {
                     codec.clear();
                     self.reset_with(codec);
                     return Err(e);

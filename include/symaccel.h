@@ -683,6 +683,11 @@ typedef struct symaccel_flac_md5_job {
  * a block longer than row_pitch, a pair mode above 3 or a pair mode with nch != 2, NULL rows, NULL frames with n_frames > 0)
  * hashes nothing: its state stays as it was and its checkpoints are that state. */
 int symaccel_flac_md5_device(symaccel_ctx *ctx, const symaccel_flac_md5_job *d_jobs, size_t n_jobs);
+/* The finishing form: the same jobs, the same hashing, and `rows` IS WRITTEN (the job struct's const notwithstanding) -- every word of
+ * a frame that was hashed is replaced by its decorrelated value `<< out_shift` (wrapping; decoder.rs:239-242), so the plane holds final
+ * PCM when the launch ends: restore -> this, instead of restore -> md5 -> decorrelate.  Words past a frame's block_len are left as
+ * they are.  A job that does not add up hashes nothing and writes nothing back; out_shift <= 31. */
+int symaccel_flac_md5_finish_device(symaccel_ctx *ctx, const symaccel_flac_md5_job *d_jobs, size_t n_jobs, uint32_t out_shift);
 /* The same for one stream in host memory (rows back to back at row_pitch); SYMACCEL_ERR_INVALID_ARG for a job that does not add
  * up.  h_checkpoints may be NULL. */
 int symaccel_flac_md5(symaccel_ctx *ctx, const int32_t *h_rows, size_t row_pitch, const symaccel_flac_md5_frame *h_frames,
@@ -896,7 +901,19 @@ int symaccel_pcm_decode(symaccel_ctx *ctx, const void *h_bytes, size_t packet_pi
  *                              in = { buf[chain][unit] i32 (warm-up samples + residuals; the RESULT overwrites it: slot.out == slot.input[0]),
  *                              desc[chain] (symaccel_flac_desc), coeffs[chain][32] i32 }; no state; param = 0.  With param = 0x100 | out_shift
  *                              the chains are channel pairs (2p, 2p + 1), in[3] = pair_mode[chain / 2] u8, and the decorrelation and the
- *                              left-justification happen in the same kernel (symaccel_flac_restore_stereo_device, decoder.rs:199-242)
+ *                              left-justification happen in the same kernel (symaccel_flac_restore_stereo_device, decoder.rs:199-242).
+ *                              THE VERIFY FORMS (the STREAMINFO MD5, validate.rs:25-75): param = 0x200 | (nch - 1) << 12, nch 1..8, n_chains
+ *                              a multiple of nch: a submission is ONE stream's run of frames (chains f * nch .. f * nch + nch - 1 are
+ *                              frame f's subframes), restored (the plain kernels) and then hashed by symaccel_flac_md5_device in the same
+ *                              launch.  in[3] = symaccel_flac_md5_frame[chain / nch] (bytes_per_sample always filled, 1..4) and ONE state
+ *                              plane, symaccel_md5_state[chain / nch]: entry 0 goes in as the stream's starting state, entry f comes back
+ *                              as the state after frame f.  The planes come back as param = 0 leaves them (the caller decorrelates and
+ *                              shifts).  param = 0x300 | out_shift | (nch - 1) << 12: the finishing form
+ *                              (symaccel_flac_md5_finish_device) -- the planes come back decorrelated (nch == 2) and `<< out_shift`.  A
+ *                              submission whose frame records do not add up (block_len above units_per_chain, pair_mode above 3 or
+ *                              non-zero with nch != 2, bytes_per_sample 0 or above 4) or whose restore descriptors do not fails alone
+ *                              with SYMACCEL_ERR_INVALID_ARG: nothing of it is hashed and every entry of its state plane comes back
+ *                              equal to entry 0 as submitted.  No output format (reserve_fmt) in these forms.
  *   SYMACCEL_BATCH_ALAC_PREDICT symaccel_alac_predict across streams, the same shape: in = { buf[chain][unit] i32 (in place), desc[chain]
  *                              (symaccel_alac_desc), coeffs[chain][32] }; param = 0.  With param = 0x100: in[3] = pair_weight[chain / 2] i32,
  *                              in[4] = pair_shift[chain / 2] u8 (symaccel_alac_predict_stereo_device, lib.rs:541-560)
@@ -1059,6 +1076,13 @@ int symaccel_batcher_submit_vorbis_decode(symaccel_batcher *b, int bs0_exp, int 
  * of one stream's batch; collect() writes the result over buf_io */
 int symaccel_batcher_submit_flac_restore(symaccel_batcher *b, int32_t *buf_io, const symaccel_flac_desc *desc, const int32_t *coeffs,
                                          const uint8_t *pair_mode, uint32_t out_shift, size_t n_blocks, size_t blocksize, uint64_t *ticket);
+/* The verify forms of SYMACCEL_BATCH_FLAC_RESTORE for n_frames frames of one stream (n_frames * nch subframes in buf_io / desc / coeffs,
+ * frame-major): finish == 0 is param 0x200 (out_shift must be 0), otherwise 0x300 | out_shift.  md5_states_io[n_frames]: entry 0 is the
+ * state the stream starts from; collect() writes the result over buf_io and the state after frame f into entry f -- for a submission
+ * that failed alone (SYMACCEL_ERR_INVALID_ARG from collect()) every entry is set to that starting state and buf_io is left alone. */
+int symaccel_batcher_submit_flac_verify(symaccel_batcher *b, int32_t *buf_io, const symaccel_flac_desc *desc, const int32_t *coeffs,
+                                        const symaccel_flac_md5_frame *frames, size_t n_frames, int nch, size_t blocksize, int finish,
+                                        uint32_t out_shift, symaccel_md5_state *md5_states_io, uint64_t *ticket);
 /* symaccel_alac_predict (pair_weight / pair_shift NULL) / symaccel_alac_predict_stereo_device for one stream's batch, in place */
 int symaccel_batcher_submit_alac_predict(symaccel_batcher *b, int32_t *buf_io, const symaccel_alac_desc *desc, const int32_t *coeffs,
                                          const int32_t *pair_weight, const uint8_t *pair_shift, size_t n_blocks, size_t blocksize,
@@ -1080,7 +1104,8 @@ int symaccel_batcher_flush(symaccel_batcher *b);
 /* "results will be wanted soon": launch the pending groups that are worth a launch of their own (4 MiB of input, or flush_bytes / 8),
  * leave smaller ones to grow -- what a decoder calls when a quarter of its current batch is left */
 int symaccel_batcher_hint(symaccel_batcher *b);
-/* bytes per chain of every plane of a kind (per submission for MP3_DECODE's input[3]); unused planes 0 */
+/* bytes per chain of every plane of a kind (per submission for MP3_DECODE's input[3]; per channel pair for the pair planes of the fused
+ * FLAC / ALAC forms; per FRAME -- nch chains -- for input[3] and the state plane of FLAC_RESTORE's verify forms); unused planes 0 */
 int symaccel_batcher_plane_bytes(int kind, int param, size_t units_per_chain, size_t *input_bytes, size_t *state_bytes, size_t *out_bytes); /* [6], [3] */
 int symaccel_batcher_get_stats(symaccel_batcher *b, symaccel_batcher_stats *out);
 

@@ -601,6 +601,32 @@ struct FinalizeResult {  // codecs/audio.rs:230-236
     std::optional<bool> verify_ok;
 };
 
+// A codec that verifies its stream (FLAC: the STREAMINFO MD5) is told about the decoder's life below it: `set_verify(bool)` (the
+// registry's AudioDecoderOptions::verify), `published(i)` when packet i of the current batch is handed out, `rewind()` when whatever
+// was computed beyond the last packet handed out is dropped (a seek, skipped packets, an error), `set_replaying(bool)` around the
+// one-packet replay, which must not count, and `finalize_result()`.
+template <class C, class = void>
+struct has_finalize_result : std::false_type {};
+template <class C>
+struct has_finalize_result<C, std::void_t<decltype(&C::finalize_result)>> : std::true_type {};
+template <class C, class = void>
+struct has_set_verify : std::false_type {};
+template <class C>
+struct has_set_verify<C, std::void_t<decltype(&C::set_verify)>> : std::true_type {};
+// (every hook is detected on its own: a codec supplies the ones it needs)
+template <class C, class = void>
+struct has_published : std::false_type {};
+template <class C>
+struct has_published<C, std::void_t<decltype(&C::published)>> : std::true_type {};
+template <class C, class = void>
+struct has_rewind : std::false_type {};
+template <class C>
+struct has_rewind<C, std::void_t<decltype(&C::rewind)>> : std::true_type {};
+template <class C, class = void>
+struct has_set_replaying : std::false_type {};
+template <class C>
+struct has_set_replaying<C, std::void_t<decltype(&C::set_replaying)>> : std::true_type {};
+
 // With a `Batcher` (second constructor) the same decoder coalesces ACROSS streams: its batches are submitted to the process-wide
 // batcher instead of being transformed by a call of their own, and the next batch is submitted early -- as soon as half of the
 // current one has been handed out -- so that by the time this stream needs it, the decoders of the other streams have submitted
@@ -708,7 +734,19 @@ public:
         return last_;
     }
 
-    FinalizeResult finalize() { return FinalizeResult{}; }  // (the f32 codecs verify nothing, like the reference's)
+    // AudioDecoder::finalize (audio.rs:283-290): the codec's verdict over the packets handed out so far (the f32 codecs verify
+    // nothing, like the reference's)
+    FinalizeResult finalize() {
+        if constexpr (has_finalize_result<Codec>::value) return codec_.finalize_result();
+        else return FinalizeResult{};
+    }
+    // AudioDecoderOptions::verify for a codec that can (before the first decode()); the others behave as ever
+    void set_verify(bool on) {
+        if constexpr (has_set_verify<Codec>::value) {
+            if (cur_live_ || next_live_ || head_ < ready_.size()) throw std::logic_error("LookaheadDecoder::set_verify: before the first decode()");
+            codec_.set_verify(on);
+        }
+    }
     const Buffer &last_decoded() const { return last_; }
     // Deliver the PCM in the caller's sample format, converted (and interleaved) in the batcher's scatter: what crosses the link is the
     // bytes the caller wants (symaccel_batcher_reserve_fmt).  decode() then keeps returning the frame count, the planar ref holds no
@@ -801,6 +839,15 @@ private:
     }
     void replay_last() {
         std::vector<Packet> one(1, last_packet_);
+        struct Replaying {  // (a verifying codec counts this packet once: when it was handed out)
+            Codec &c;
+            explicit Replaying(Codec &codec) : c(codec) {
+                if constexpr (has_set_replaying<Codec>::value) c.set_replaying(true);
+            }
+            ~Replaying() {
+                if constexpr (has_set_replaying<Codec>::value) c.set_replaying(false);
+            }
+        } replaying(codec_);
         if (batcher_) {
             if constexpr (Codec::kBatchKind != 0) {  // (through the batcher: the context is not ours to call while a batcher drives it)
                 submit(one);
@@ -903,6 +950,7 @@ private:
         }
     }
     void drop_tickets() {
+        if constexpr (has_rewind<Codec>::value) codec_.rewind();
         if (!batcher_) return;
         if (next_live_) {
             symaccel_batcher_wait(batcher_->raw(), next_ticket_, nullptr);  // (its result is not wanted, its slot must be idle)
@@ -923,6 +971,7 @@ private:
         head_ = 0;
     }
     void publish(std::size_t i) {
+        if constexpr (has_published<Codec>::value) codec_.published(i);
         // where packet i of the last batch lies in a channel's plane is the codec's business: fixed-size frames are
         // [channel][packet][frames]; Vorbis packs (prev_n + n) / 4 samples per packet and none for the first one
         const std::size_t nch = codec_.channels();
@@ -1681,6 +1730,8 @@ struct Flac {
         std::size_t channels = 2;
         std::uint32_t bits_per_sample = 16;
         std::size_t max_blocksize = 4096;  // STREAMINFO's maximum block size: the slot every subframe gets with the batcher
+        bool verify = false;               // AudioDecoderOptions::verify: hash the decoded audio (validate.rs:25-75) ...
+        std::optional<std::array<std::uint8_t, 16>> expected_md5;  // ... and compare with STREAMINFO's digest, if it has one (decoder.rs:272-308)
     };
     struct Packet {
         std::uint64_t ts = 0;
@@ -1690,19 +1741,53 @@ struct Flac {
         std::vector<std::int32_t> coeffs;       // [channel][32], reference order (decoder.rs:716-752)
         std::uint8_t pair_mode = 0;             // 0 independent, 1 left/side, 2 mid/side, 3 right/side (two-channel frames)
     };
-    explicit Flac(const Params &p) : nch_(p.channels), shift_(32u - p.bits_per_sample), max_bs_(p.max_blocksize) {
+    explicit Flac(const Params &p) : nch_(p.channels), shift_(32u - p.bits_per_sample), max_bs_(p.max_blocksize), expected_(p.expected_md5) {
         if (p.channels == 0 || p.bits_per_sample == 0 || p.bits_per_sample > 32 || p.max_blocksize == 0 || p.max_blocksize > 65535)
             throw std::invalid_argument("Flac: parameters");
+        symaccel_md5_init(&published_);
+        chain_end_ = published_;
+        set_verify(p.verify);
+    }
+    // Verification (the STREAMINFO MD5): the batches go through the verify forms of the kind -- restore, then one MD5 wavefront per
+    // stream in the same launch, the state after every frame coming back as a checkpoint.  `published_` is the state after the last
+    // packet handed out, `chain_end_` the state after the last frame of the most recently computed batch (what the next batch starts
+    // from); a seek or a skip drops the difference (the reference's reset() leaves its validator alone, decoder.rs:254-256).
+    void set_verify(bool on) {
+        if (on && nch_ > 8) throw Error(Error::Kind::Unsupported, SYMACCEL_ERR_UNSUPPORTED, "flac: verification of more than 8 channels");
+        verify_ = on;
+    }
+    void set_replaying(bool on) { replaying_ = on; }
+    void published(std::size_t i) {
+        if (verify_ && i < cps_.size()) published_ = cps_[i];
+    }
+    void rewind() { chain_end_ = published_; }
+    FinalizeResult finalize_result() {
+        FinalizeResult r;
+        if (verify_ && expected_) {  // (no digest in STREAMINFO: the reference only warns, decoder.rs:302-304)
+            std::array<std::uint8_t, 16> got{};
+            symaccel_md5_digest(&published_, got.data());
+            r.verify_ok = got == *expected_;
+        }
+        return r;
+    }
+    std::array<std::uint8_t, 16> md5_so_far() const {  // the digest over the packets handed out so far
+        std::array<std::uint8_t, 16> got{};
+        symaccel_md5_digest(&published_, got.data());
+        return got;
     }
     // With the batcher (SYMACCEL_BATCH_FLAC_RESTORE) a chain is ONE SUBFRAME and the unit count is the stream's maximum block size, so
     // the batches of every FLAC stream with that block size share launches whatever their lengths; a two-channel stream takes the
     // fused form (param 0x100 | shift: decorrelation and left-justification in the restore kernel's write-back, decoder.rs:199-242),
-    // every other layout the plain one with the shift on the host.
+    // every other layout the plain one with the shift on the host.  Verifying, the same split: 0x300 | shift (the finishing MD5 kernel
+    // leaves the pair decorrelated and left-justified) for two channels, 0x200 otherwise.
     static constexpr int kBatchKind = SYMACCEL_BATCH_FLAC_RESTORE;
     static constexpr bool kDirect = false;
     struct BatchView {};
     void attach(Batcher &) {}
-    int batch_param() const { return nch_ == 2 ? (int)(0x100u | shift_) : 0; }
+    int batch_param() const {
+        if (hashing()) return (nch_ == 2 ? (int)(0x300u | shift_) : 0x200) | (int)((nch_ - 1) << 12);
+        return nch_ == 2 ? (int)(0x100u | shift_) : 0;
+    }
     std::size_t batch_chains(std::size_t k) const { return k * nch_; }
     std::size_t batch_units(std::size_t) const { return max_bs_; }
     void fill_slot(const std::vector<Packet> &batch, const symaccel_batch_slot &slot) {
@@ -1724,12 +1809,21 @@ struct Flac {
                 desc[i * nch_ + c] = p.desc[c];
                 std::copy_n(p.coeffs.data() + c * 32, 32, coeffs + (i * nch_ + c) * 32);
             }
-            if (nch_ == 2) static_cast<std::uint8_t *>(slot.input[3])[i] = p.pair_mode;
+            if (hashing()) static_cast<symaccel_flac_md5_frame *>(slot.input[3])[i] = md5_frame(p);
+            else if (nch_ == 2) static_cast<std::uint8_t *>(slot.input[3])[i] = p.pair_mode;
         }
+        if (hashing()) static_cast<symaccel_md5_state *>(slot.state[0])[0] = chain_end_;
     }
     void take_state(const symaccel_batch_slot &slot) {
         lens_.swap(next_lens_);
         stride_ = max_bs_;
+        if (hashing()) {  // entry f: the state after frame f
+            const symaccel_md5_state *st = static_cast<const symaccel_md5_state *>(slot.state[0]);
+            cps_.assign(st, st + lens_.size());
+            if (!cps_.empty()) chain_end_ = cps_.back();
+        } else {
+            cps_.clear();
+        }
         if (nch_ != 2) {  // decoder.rs:239-242 (the two-channel form did it on the device)
             std::int32_t *words = static_cast<std::int32_t *>(slot.out);
             for (std::size_t i = 0; i < slot.out_bytes / 4; ++i) words[i] = (std::int32_t)((std::uint32_t)words[i] << shift_);
@@ -1768,6 +1862,13 @@ struct Flac {
             modes_[i] = p.pair_mode;
         }
         check(symaccel_flac_restore(ctx.raw(), pcm.data(), desc_.data(), coeffs_.data(), k * nch_, stride_), ctx.raw());
+        cps_.clear();
+        if (hashing() && k) {  // the restored words, before the decorrelation and the shift: what the reference hashes (decoder.rs:231-234)
+            frames_.resize(k);
+            for (std::size_t i = 0; i < k; ++i) frames_[i] = md5_frame(batch[i]);
+            cps_.resize(k);
+            check(symaccel_flac_md5(ctx.raw(), pcm.data(), stride_, frames_.data(), k, (int)nch_, (int)bytes_per_sample(), &chain_end_, cps_.data()), ctx.raw());
+        }
         if (nch_ == 2) {
             // pair i = (channel 0, channel 1) of packet i: rows 2 i and 2 i + 1 of the batch
             ch0_.resize(k * stride_);
@@ -1787,9 +1888,19 @@ struct Flac {
     }
 
 private:
+    bool hashing() const { return verify_ && !replaying_; }
+    unsigned bytes_per_sample() const { return (32u - shift_ + 7) / 8; }  // validate.rs:39-45
+    symaccel_flac_md5_frame md5_frame(const Packet &p) const {
+        return symaccel_flac_md5_frame{(std::uint16_t)p.blocksize, p.pair_mode, (std::uint8_t)bytes_per_sample()};
+    }
     std::size_t nch_;
     std::uint32_t shift_;
     std::size_t max_bs_;
+    std::optional<std::array<std::uint8_t, 16>> expected_;
+    bool verify_ = false, replaying_ = false;
+    symaccel_md5_state published_{}, chain_end_{};
+    std::vector<symaccel_md5_state> cps_;  // the state after every packet of the current batch
+    std::vector<symaccel_flac_md5_frame> frames_;
     std::size_t stride_ = 0;
     std::vector<std::size_t> lens_, next_lens_;
     std::vector<symaccel_flac_desc> desc_;
@@ -2063,7 +2174,9 @@ public:
     std::unique_ptr<LookaheadDecoder<Codec>> make_audio_decoder(const typename Codec::Params &params, const AudioDecoderOptions &opts,
                                                                 typename LookaheadDecoder<Codec>::Peek peek) const {
         require<Codec>();
-        return std::make_unique<LookaheadDecoder<Codec>>(Batcher::shared(), params, opts.lookahead, std::move(peek));
+        auto dec = std::make_unique<LookaheadDecoder<Codec>>(Batcher::shared(), params, opts.lookahead, std::move(peek));
+        if (opts.verify) dec->set_verify(true);  // (a codec without set_verify decodes as ever: the reference's verify nothing either)
+        return dec;
     }
     // (zero-copy parse, for the codecs with kDirect)
     template <class Codec>

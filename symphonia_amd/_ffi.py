@@ -68,6 +68,7 @@ ABI_SYMBOLS = [
     "symaccel_batcher_submit_vorbis_decode", "symaccel_batcher_submit_flac_restore", "symaccel_batcher_submit_alac_predict",
     "symaccel_flac_restore_strided_device", "symaccel_alac_predict_strided_device", "symaccel_row_stride",
     "symaccel_md5_init", "symaccel_md5_update", "symaccel_md5_digest", "symaccel_flac_md5_device", "symaccel_flac_md5",
+    "symaccel_flac_md5_finish_device", "symaccel_batcher_submit_flac_verify",
     "symaccel_sample_bytes", "symaccel_pcm_convert_device", "symaccel_pcm_convert",
     "symaccel_batcher_reserve_fmt", "symaccel_batcher_submit_fmt",
     "symaccel_adpcm_block_bytes", "symaccel_adpcm_decode_device", "symaccel_adpcm_decode",
@@ -247,6 +248,8 @@ class Library:
         d.symaccel_md5_update.argtypes = [_vp, _vp, _sz]
         d.symaccel_md5_digest.argtypes = [_vp, _vp]
         d.symaccel_flac_md5_device.argtypes = [_vp, _vp, _sz]
+        d.symaccel_flac_md5_finish_device.argtypes = [_vp, _vp, _sz, _u32]
+        d.symaccel_batcher_submit_flac_verify.argtypes = [_vp, _vp, _vp, _vp, _vp, _sz, _i, _sz, _i, _u32, _vp, C.POINTER(C.c_uint64)]
         d.symaccel_flac_md5.argtypes = [_vp, _vp, _sz, _vp, _sz, _i, _i, _vp, _vp]
         d.symaccel_sample_bytes.argtypes = [_i]
         d.symaccel_sample_bytes.restype = _sz

@@ -744,6 +744,13 @@ def flac_md5_device(ctx, jobs, n_jobs=None):
     ctx._call(ctx.lib.dll.symaccel_flac_md5_device, _ptr(jobs), n)
 
 
+def flac_md5_finish_device(ctx, jobs, out_shift, n_jobs=None):
+    """symaccel_flac_md5_finish_device: as flac_md5_device, and the jobs' rows ARE WRITTEN -- every hashed word is replaced by its
+    decorrelated value << out_shift (final PCM)."""
+    n = int(n_jobs) if n_jobs is not None else (jobs.numel() if _is_torch(jobs) else jobs.nbytes) // FLAC_MD5_JOB_DTYPE.itemsize
+    ctx._call(ctx.lib.dll.symaccel_flac_md5_finish_device, _ptr(jobs), n, int(out_shift))
+
+
 # ---- PCM in the caller's sample format (symaccel_pcm_convert) --------------------------------------------------------------------
 FMT_U8, FMT_S8, FMT_U16, FMT_S16, FMT_U24, FMT_S24, FMT_U32, FMT_S32, FMT_F32 = (_ffi.FMT_U8, _ffi.FMT_S8, _ffi.FMT_U16, _ffi.FMT_S16, _ffi.FMT_U24,
                                                                                  _ffi.FMT_S24, _ffi.FMT_U32, _ffi.FMT_S32, _ffi.FMT_F32)
@@ -1184,6 +1191,22 @@ class Batcher:
         self._check(self.dll.symaccel_batcher_submit_flac_restore(
             self.handle, buf_io.ctypes.data, desc.ctypes.data, coeffs.ctypes.data, pair_mode.ctypes.data if pair_mode is not None else None,
             int(out_shift), n_blocks, blocksize, C.byref(t)))
+        return int(t.value)
+
+    def submit_flac_verify(self, buf_io, desc, coeffs, frames, nch, states_io, finish=False, out_shift=0):
+        """symaccel_batcher_submit_flac_verify: ONE stream's run of frames, restored and then hashed (the STREAMINFO MD5) in the same
+        launch.  buf_io [frame * nch + channel][blocksize] i32, desc / coeffs per subframe, frames FLAC_MD5_FRAME_DTYPE[n_frames] (every
+        bytes_per_sample 1..4), states_io MD5_STATE_DTYPE[n_frames]: entry 0 is the starting state, collect() writes the state after frame
+        f into entry f.  finish: the planes come back decorrelated (nch == 2) and << out_shift, else as submit_flac_restore leaves them."""
+        n_blocks, blocksize = int(buf_io.shape[0]), int(buf_io.shape[1])
+        assert frames.dtype == FLAC_MD5_FRAME_DTYPE and states_io.dtype == MD5_STATE_DTYPE and len(states_io) == len(frames)
+        assert n_blocks == len(frames) * int(nch)
+        for a in (buf_io, desc, coeffs, frames, states_io):
+            assert a.flags["C_CONTIGUOUS"]
+        t = C.c_uint64()
+        self._check(self.dll.symaccel_batcher_submit_flac_verify(
+            self.handle, buf_io.ctypes.data, desc.ctypes.data, coeffs.ctypes.data, frames.ctypes.data, len(frames), int(nch), blocksize,
+            int(bool(finish)), int(out_shift), states_io.ctypes.data, C.byref(t)))
         return int(t.value)
 
     def submit_alac_predict(self, buf_io, desc, coeffs, pair_weight=None, pair_shift=None):

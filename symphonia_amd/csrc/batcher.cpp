@@ -107,14 +107,21 @@ bool plane_sizes(int kind, int param, size_t units, PlaneSizes *ps) {
         ps->out = units * 2304;
         return true;
     case SYMACCEL_BATCH_FLAC_RESTORE:  // symaccel_flac_restore(_stereo_device): buf (in place), desc, coeffs [, pair_mode]; units = block size
-        if (units > 65535 || (param & ~0x11f)) return false;  // frame.rs:58 (u16 block size); param = 0, or 0x100 | out_shift
-        ps->n_in = pair_param(param).pairs ? 4 : 3;
+        // frame.rs:58 (u16 block size); param = 0, or 0x100 | out_shift; the verify forms 0x200 | (nch - 1) << 12 and 0x300 | out_shift | (nch - 1) << 12
+        if (units > 65535 || param < 0 || (param & ~((param & 0x200) ? 0x731f : 0x11f)) || ((param & 0x300) == 0x200 && (param & 31))) return false;
+        ps->n_in = pair_param(param).pairs || flac_verify_param(param).verify ? 4 : 3;
         ps->in[0] = units * 4;
         ps->in[1] = sizeof(symaccel_flac_desc);
         ps->in[2] = 32 * 4;
         if (pair_param(param).pairs) {
             ps->in[3] = 1;
             ps->in_div[3] = 2;
+        }
+        if (flac_verify_param(param).verify) {  // a frame record and a state per FRAME: entry 0 in, every frame's checkpoint out
+            ps->in[3] = sizeof(symaccel_flac_md5_frame);
+            ps->in_div[3] = ps->state_div = (uint8_t)flac_verify_param(param).nch;
+            ps->n_state = 1;
+            ps->state[0] = sizeof(symaccel_md5_state);
         }
         ps->in_place = true;
         return true;
@@ -197,7 +204,7 @@ SlotLayout slot_layout(const PlaneSizes &ps, size_t n_chains) {
     }
     for (int i = 0; i < ps.n_state; ++i) {
         l.state[i] = off;
-        l.state_bytes[i] = ps.state[i] * n_chains;
+        l.state_bytes[i] = ps.state[i] * (n_chains / ps.state_div);
         off += round256(l.state_bytes[i]);
     }
     if (ps.in_place) {
@@ -300,6 +307,7 @@ struct Group {
     Mp3Lists mp3;               // the lists of the kind the group is of (batcher_lists.h)
     AacLists aac;
     VorbisLists vb;
+    FlacVerifyLists fv;
 };
 
 // One pipeline: a context (kernel stream, scratch, tables) and two copy streams.  Lane 0 is the caller's context; the others are the
@@ -443,6 +451,13 @@ inline bool vorbis_kind(int kind) { return kind == SYMACCEL_BATCH_VORBIS_SYNTH |
 // ---- what a FLAC / ALAC / ADPCM submission's descriptors say, judged alone (its neighbours in the launch are not failed for it; the
 // kinds that have lists judge theirs in batcher_lists.h); then the steps of a launch (launch_group_inner) in their order
 int check_flac(size_t units, int param, const TicketView &v) {
+    const FlacVerifyParam vp = flac_verify_param(param);
+    if (vp.verify) {  // the frame records, as flac_md5_kernel judges a job -- and every frame names its width
+        const symaccel_flac_md5_frame *fr = v.in<const symaccel_flac_md5_frame>(3);
+        for (size_t f = 0; f < v.n_chains / vp.nch; ++f)
+            if (fr[f].block_len > units || fr[f].pair_mode > 3 || (fr[f].pair_mode != 0 && vp.nch != 2) || fr[f].bytes_per_sample < 1 || fr[f].bytes_per_sample > 4)
+                return SYMACCEL_ERR_INVALID_ARG;
+    }
     const symaccel_flac_desc *d = v.in<const symaccel_flac_desc>(1);
     for (size_t c = 0; c < v.n_chains; ++c) {  // what symaccel_flac_restore checks (decoder.rs:361, 456-458, 506-508)
         if (d[c].kind > SYMACCEL_FLAC_LPC || d[c].order > units || d[c].shift > 31 || d[c].wasted_bits > 31) return SYMACCEL_ERR_INVALID_ARG;
@@ -540,6 +555,12 @@ void validate_and_count(Group *g) {
         if (g->kind == SYMACCEL_BATCH_ADPCM_DECODE) v.status = check_adpcm(g->units, g->param, v);
         if (g->kind == SYMACCEL_BATCH_MPA12_DECODE) v.status = check_mpa12(g->units, g->param, v);
         if (v.status == SYMACCEL_OK) v.status = v.fmt_status;
+        // a verify submission that failed is not hashed (its job has no state: FlacVerifyLists::build), and its state plane is not
+        // brought back: every entry is its starting state from here on
+        if (g->kind == SYMACCEL_BATCH_FLAC_RESTORE && flac_verify_param(g->param).verify && v.status != SYMACCEL_OK) {
+            symaccel_md5_state *st = v.state<symaccel_md5_state>(0);
+            for (size_t f = 1; f < v.n_chains / g->ps.state_div; ++f) st[f] = st[0];
+        }
     }
     // FLAC / ALAC: the device plane's rows at the pitch the lane-per-block kernels run fastest at (symaccel_row_stride: rows 4 / 8 / 16 / 32 KiB apart -- the
     // 4096-sample blocks of nearly every stream -- put a wavefront's 64 row segments on a fraction of the HBM channels); the slots stay compact, the
@@ -555,7 +576,7 @@ size_t piece_bound(const Group *g) {
     for (const TicketView &v : g->views) {
         for (int i = 0; i < ps.n_in; ++i)
             if (!ps.in_host_only[i]) bound += pieces_of(plane_bytes(ps, i, v.n_chains));         // every plane that is copied, rounded up
-        for (int i = 0; i < ps.n_state; ++i) bound += 2 * pieces_of(ps.state[i] * v.n_chains);  // the state, in and out
+        for (int i = 0; i < ps.n_state; ++i) bound += 2 * pieces_of(ps.state[i] * (v.n_chains / ps.state_div));  // the state, in and out
         bound += pieces_of(ps.out_per_chain() * v.n_chains);                                     // the PCM
         if (v.out_fmt) {  // ... or its converting pieces: a tile of frames each, the last of every interleave group rounded up
             const size_t tile = pcm_tile_frames(v.channels, (unsigned)symaccel_sample_bytes(v.out_fmt));
@@ -564,6 +585,7 @@ size_t piece_bound(const Group *g) {
         if (g->kind == SYMACCEL_BATCH_AAC_DECODE) bound += pieces_of(ps.in[2] * v.n_chains);  // the joint-stereo rows of the blob
     }
     bound += g->tickets + 8;                                // the unit list's pieces, one per chunk at most
+    if (g->kind == SYMACCEL_BATCH_FLAC_RESTORE && flac_verify_param(g->param).verify) bound += 2 * g->tickets + 8;  // the job table's, likewise
     if (g->row_pitch) bound += 2 * g->chains;               // rows go one by one, in and out, each rounded up
     if (vorbis_kind(g->kind)) bound += 2 * g->chains;       // spectra and PCM go chain by chain, each rounded up
     if (g->kind == SYMACCEL_BATCH_AAC_DECODE) bound += 3 * g->tickets + 8;  // pair list, filters, TNS pair frames: one piece list each per chunk
@@ -593,13 +615,14 @@ void request_block(Group *g, size_t bound, BatchCopyDesc **descs, Carver &dev, C
         dev.want(&g->d_in[i], ps.in_per_ticket[i] ? ps.in[i] * g->tickets : (i == 0 && g->row_pitch ? g->row_pitch : ps.in[i]) * ((g->chains + ps.in_div[i] - 1) / ps.in_div[i]));
     }
     for (int i = 0; i < ps.n_state; ++i) {
-        dev.want(&g->d_state_in[i], ps.state[i] * g->chains);
-        dev.want(&g->d_state_out[i], ps.state[i] * g->chains);
+        dev.want(&g->d_state_in[i], ps.state[i] * (g->chains / ps.state_div));
+        dev.want(&g->d_state_out[i], ps.state[i] * (g->chains / ps.state_div));
     }
     if (ps.in_place) g->d_out = g->d_in[0];
     else dev.want(&g->d_out, ps.out * g->chains);
     g->mp3.request(dev, host, g->tickets);  // (by every kind: the blocks keep the sizes -- and the statistics their group_allocs -- they had)
     if (g->kind == SYMACCEL_BATCH_AAC_DECODE) g->aac.request(dev, host, g->chains, g->units);
+    if (g->kind == SYMACCEL_BATCH_FLAC_RESTORE && flac_verify_param(g->param).verify) g->fv.request(dev, host, g->tickets);
     if (g->kind == SYMACCEL_BATCH_VORBIS_DECODE) g->vb.request(dev, host, g->chains, vorbis_param(g->param, g->units).cap);
 }
 
@@ -658,8 +681,8 @@ Chunk next_chunk(const Group *g, size_t t0) {
     for (int i = 0; i < ps.n_in; ++i)
         if (g->d_in[i]) ch.in[i] = g->d_in[i] + (ps.in_per_ticket[i] ? t0 * ps.in[i] : (ch.c0 / ps.in_div[i]) * (i == 0 && g->row_pitch ? g->row_pitch : ps.in[i]));
     for (int i = 0; i < ps.n_state; ++i) {
-        ch.si[i] = g->d_state_in[i] + ch.c0 * ps.state[i];
-        ch.so[i] = g->d_state_out[i] + ch.c0 * ps.state[i];
+        ch.si[i] = g->d_state_in[i] + ch.c0 / ps.state_div * ps.state[i];
+        ch.so[i] = g->d_state_out[i] + ch.c0 / ps.state_div * ps.state[i];
     }
     ch.out = ps.in_place ? ch.in[0] : g->d_out + ch.c0 * ps.out;
     return ch;
@@ -678,6 +701,7 @@ void gather_rows(const Group *g, const TicketView &t, Pieces &pw) {
 // gather: the submissions' planes into the chain-major device arrays, and the chunk's lists
 void build_gather(Group *g, const Chunk &ch, Pieces &pw) {
     const PlaneSizes &ps = g->ps;
+    const bool verify = g->kind == SYMACCEL_BATCH_FLAC_RESTORE && flac_verify_param(g->param).verify;
     for (size_t ti = ch.t0; ti < ch.t0 + ch.nt; ++ti) {
         const TicketView &t = g->views[ti];
         for (int i = 0; i < ps.n_in; ++i) {
@@ -686,11 +710,23 @@ void build_gather(Group *g, const Chunk &ch, Pieces &pw) {
             else if (i == 0 && g->row_pitch) gather_rows(g, t, pw);
             else pw.bulk(t.slot + t.lay.in[i], g->d_in[i] + (ps.in_per_ticket[i] ? ti : (size_t)t.first_chain / ps.in_div[i]) * ps.in[i], t.lay.in_bytes[i]);
         }
-        for (int i = 0; i < ps.n_state; ++i) pw.add(t.slot + t.lay.state[i], g->d_state_in[i] + (size_t)t.first_chain * ps.state[i], t.lay.state_bytes[i]);
+        // (the verify forms of FLAC_RESTORE read entry 0 of a submission's state plane alone, its starting state: only that goes up)
+        for (int i = 0; i < ps.n_state; ++i) pw.add(t.slot + t.lay.state[i], g->d_state_in[i] + (size_t)t.first_chain / ps.state_div * ps.state[i], verify ? ps.state[i] : t.lay.state_bytes[i]);
     }
+    if (verify)
+        g->fv.build(g->views, ch, flac_verify_param(g->param).nch, g->d_in[0], g->row_pitch ? g->row_pitch : ps.in[0], g->d_in[3], g->d_state_in[0], g->d_state_out[0], pw);
     if (g->kind == SYMACCEL_BATCH_MP3_DECODE) g->mp3.build(g->views, ch, pw);
     if (g->kind == SYMACCEL_BATCH_AAC_DECODE) g->aac.build(g->views, ch, g->units, pw);
     if (g->kind == SYMACCEL_BATCH_VORBIS_DECODE) g->vb.build(g->views, ch, vorbis_param(g->param, g->units), g->units, pw);
+}
+
+// The verify forms of FLAC_RESTORE: the unfused restore at the group's row pitch, then ONE MD5 launch over the chunk's submissions, a
+// wavefront each (FINISH: it also leaves the planes decorrelated and left-justified).  Both on the lane's stream: the chain of this
+// group (~1 us per 64-byte block per stream) overlaps the copies and the restore of the next group on another lane.
+int launch_flac_verify(symaccel_ctx *ctx, Group *g, const Chunk &ch) {
+    const FlacVerifyParam vp = flac_verify_param(g->param);
+    SYM_TRY(launch_flac_restore(ctx, (int32_t *)ch.in[0], (const symaccel_flac_desc *)ch.in[1], (const int32_t *)ch.in[2], ch.nc, g->units, nullptr, 0, g->row_pitch / 4));
+    return g->fv.run(ctx, ch, vp.finish, vp.shift);
 }
 
 // the kernels of one chunk
@@ -712,6 +748,7 @@ int launch_chunk(symaccel_ctx *ctx, Group *g, const Chunk &ch) {
     case SYMACCEL_BATCH_VORBIS_DECODE: return g->vb.run(ctx, ch, vorbis_param(g->param, g->units), g->units);
     case SYMACCEL_BATCH_FLAC_RESTORE: {  // decoder.rs:663-752 (+ :32-82, :239-242 with the pair modes)
         const PairParam pp = pair_param(g->param);
+        if (flac_verify_param(g->param).verify) return launch_flac_verify(ctx, g, ch);
         return launch_flac_restore(ctx, (int32_t *)in[0], (const symaccel_flac_desc *)in[1], (const int32_t *)in[2], ch.nc, g->units,
                                    pp.pairs ? (const uint8_t *)in[3] : nullptr, pp.shift, g->row_pitch / 4);
     }
@@ -759,6 +796,7 @@ bool scatter_converted(const Group *g, const TicketView &t, size_t plane_pitch, 
 void build_scatter(const Group *g, const Chunk &ch, Pieces &pw, size_t *pcm_stride) {
     const PlaneSizes &ps = g->ps;
     const size_t plane_pitch = g->row_pitch ? g->row_pitch : ps.out_per_chain();  // bytes between the chains of d_out
+    const bool verify = g->kind == SYMACCEL_BATCH_FLAC_RESTORE && flac_verify_param(g->param).verify;
     bool converting = false;
     for (size_t ti = ch.t0; ti < ch.t0 + ch.nt; ++ti) {
         const TicketView &t = g->views[ti];
@@ -771,7 +809,8 @@ void build_scatter(const Group *g, const Chunk &ch, Pieces &pw, size_t *pcm_stri
         } else {
             pw.bulk(g->d_out + (size_t)t.first_chain * plane_pitch, t.slot + t.lay.out, t.lay.out_bytes);
         }
-        for (int i = 0; i < ps.n_state; ++i) pw.add(g->d_state_out[i] + (size_t)t.first_chain * ps.state[i], t.slot + t.lay.state[i], t.lay.state_bytes[i]);
+        if (verify && t.status != SYMACCEL_OK) continue;  // (a verify submission that failed was not hashed: validate_and_count left its states in the slot)
+        for (int i = 0; i < ps.n_state; ++i) pw.add(g->d_state_out[i] + (size_t)t.first_chain / ps.state_div * ps.state[i], t.slot + t.lay.state[i], t.lay.state_bytes[i]);
     }
     *pcm_stride = converting ? plane_pitch / 4 : 0;
 }
@@ -1163,7 +1202,8 @@ int symaccel_batcher_reserve_fmt(symaccel_batcher *b, int kind, int param, size_
     if (kind == SYMACCEL_BATCH_MP3_DECODE && n_chains > 2) return SYMACCEL_ERR_INVALID_ARG;            // one stream per submission
     if (kind == SYMACCEL_BATCH_VORBIS_DECODE && n_chains != (size_t)vorbis_param(param, units_per_chain).nch) return SYMACCEL_ERR_INVALID_ARG;  // one stream per submission
     for (int i = 0; i < ps.n_in; ++i)
-        if (ps.in_div[i] == 2 && (n_chains & 1)) return SYMACCEL_ERR_INVALID_ARG;  // channel pairs
+        if (n_chains % ps.in_div[i] != 0) return SYMACCEL_ERR_INVALID_ARG;  // channel pairs; whole frames of a verified FLAC stream
+    if (kind == SYMACCEL_BATCH_FLAC_RESTORE && flac_verify_param(param).verify && out_fmt != 0) return SYMACCEL_ERR_INVALID_ARG;
     Locked locked(b);
     std::unique_lock<std::mutex> &lock = locked.lock;
     if (kind == SYMACCEL_BATCH_AAC_DECODE && param != -1 && (param < 0 || (size_t)param >= b->bands.size())) return SYMACCEL_ERR_INVALID_ARG;  // (symaccel_batcher_aac_bands first; -1: no pairs, no table)
@@ -1548,6 +1588,16 @@ int symaccel_batcher_submit_flac_restore(symaccel_batcher *b, int32_t *buf_io, c
     return symaccel_batcher_submit(b, SYMACCEL_BATCH_FLAC_RESTORE, pair_mode ? (int)(0x100 | out_shift) : 0, n_blocks, blocksize, in, st, buf_io, ticket);
 }
 
+int symaccel_batcher_submit_flac_verify(symaccel_batcher *b, int32_t *buf_io, const symaccel_flac_desc *desc, const int32_t *coeffs,
+                                        const symaccel_flac_md5_frame *frames, size_t n_frames, int nch, size_t blocksize, int finish, uint32_t out_shift,
+                                        symaccel_md5_state *md5_states_io, uint64_t *ticket) {
+    if (nch < 1 || nch > 8 || out_shift > 31 || (!finish && out_shift) || n_frames > 0x7fffffffu / 8) return SYMACCEL_ERR_INVALID_ARG;
+    const void *in[kMaxIn] = {buf_io, desc, coeffs, frames, nullptr, nullptr};
+    void *st[3] = {md5_states_io, nullptr, nullptr};
+    const int param = (finish ? (int)(0x300 | out_shift) : 0x200) | (nch - 1) << 12;
+    return symaccel_batcher_submit(b, SYMACCEL_BATCH_FLAC_RESTORE, param, n_frames * (size_t)nch, blocksize, in, st, buf_io, ticket);
+}
+
 int symaccel_batcher_submit_adpcm_decode(symaccel_batcher *b, const uint8_t *bytes, int codec, size_t channels, size_t n_blocks, size_t block_bytes,
                                         int32_t *pcm, uint64_t *ticket) {
     if (codec < 0 || codec > 255 || channels > 255) return SYMACCEL_ERR_INVALID_ARG;
@@ -1576,10 +1626,12 @@ int symaccel_batcher_collect(symaccel_batcher *b, uint64_t ticket) {
     if (!b) return SYMACCEL_ERR_INVALID_ARG;
     symaccel_batch_slot slot;
     void *user_state[kMaxState], *user_out;
+    bool verify;
     {
         Locked locked(b);
         Ticket *t = find_ticket(b, ticket);
         if (!t || !t->user_out) return SYMACCEL_ERR_INVALID_ARG;
+        verify = t->group->kind == SYMACCEL_BATCH_FLAC_RESTORE && flac_verify_param(t->group->param).verify;
         for (int i = 0; i < kMaxState; ++i) user_state[i] = t->user_state[i];
         user_out = t->user_out;
     }
@@ -1588,6 +1640,8 @@ int symaccel_batcher_collect(symaccel_batcher *b, uint64_t ticket) {
         std::memcpy(user_out, slot.out, slot.out_bytes);
         for (int i = 0; i < kMaxState; ++i)
             if (user_state[i] && slot.state[i]) std::memcpy(user_state[i], slot.state[i], slot.state_bytes[i]);
+    } else if (verify && st == SYMACCEL_ERR_INVALID_ARG && user_state[0] && slot.state[0]) {
+        std::memcpy(user_state[0], slot.state[0], slot.state_bytes[0]);  // (failed alone: every entry is the starting state)
     }
     const int rel = symaccel_batcher_release(b, ticket);
     return st != SYMACCEL_OK ? st : rel;

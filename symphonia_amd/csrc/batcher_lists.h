@@ -26,6 +26,7 @@ struct PlaneSizes {
     bool in_host_only[kMaxIn] = {false, false, false, false, false, false};  // read by the host when the group is launched; never copied as it is
     uint8_t in_div[kMaxIn] = {1, 1, 1, 1, 1, 1};                             // 2: one element per channel PAIR (chains 2p, 2p + 1)
     size_t state[kMaxState] = {0, 0, 0};
+    uint8_t state_div = 1;  // k: the state planes hold one element per k chains (the verify forms of FLAC_RESTORE: one per frame)
     size_t out = 0;
     bool in_place = false;  // the result overwrites input[0] (FLAC / ALAC: the entry points they stand for work in place)
     int n_in = 0, n_state = 0;
@@ -58,7 +59,15 @@ struct PairParam {  // FLAC_RESTORE: 0, or 0x100 | out_shift; ALAC_PREDICT: 0 or
     bool pairs;
     uint32_t shift;
 };
-inline PairParam pair_param(int param) { return {(param & 0x100) != 0, (uint32_t)(param & 31)}; }
+inline PairParam pair_param(int param) { return {(param & 0x300) == 0x100, (uint32_t)(param & 31)}; }
+struct FlacVerifyParam {  // FLAC_RESTORE: 0x200 | (nch - 1) << 12, or 0x300 | out_shift | (nch - 1) << 12 -- restore, then the STREAMINFO MD5
+    bool verify, finish;
+    uint32_t shift;
+    unsigned nch;
+};
+inline FlacVerifyParam flac_verify_param(int param) {
+    return {(param & 0x200) != 0, (param & 0x300) == 0x300, (uint32_t)(param & 31), (param & 0x200) ? (unsigned)((param >> 12) & 7) + 1 : 1u};
+}
 
 // Vorbis: how much of a chain's spectrum / PCM plane its blocks fill (lines of the packed spectrum; samples of the packed PCM:
 // lib.rs:303 -- a block yields (prev_n + n) / 4, the first block after a reset keeps n / 2 slots): only that much crosses the link
@@ -166,6 +175,34 @@ struct Mp3Lists {
                                  (const float *)ch.si[1], (const int32_t *)ch.si[2], (float *)ch.so[0], (float *)ch.so[1], (int32_t *)ch.so[2],
                                  (float *)ch.out, ch.nc, units);
     }
+};
+
+// ------------------------------------------------------------------------------------------------ FLAC_RESTORE, the verify forms
+// One symaccel_flac_md5_job per submission (a submission is one stream's run of frames): its rows in the device plane at the group's
+// pitch, its ranges of the frame plane (in[3]) and of the two state planes -- the starting state is entry 0 of the plane that went in,
+// the checkpoints fill the plane that goes back.  A submission that failed gets state = NULL: the kernel skips it.
+struct FlacVerifyLists {
+    symaccel_flac_md5_job *d_jobs = nullptr, *h_jobs = nullptr;
+    void request(Carver &dev, Carver &host, size_t tickets) { want_both(dev, host, &d_jobs, &h_jobs, tickets * sizeof(symaccel_flac_md5_job)); }
+    void build(const std::vector<TicketView> &views, const Chunk &ch, unsigned nch, char *d_rows, size_t pitch_bytes, char *d_frames, char *d_state_in,
+               char *d_state_out, Pieces &pw) {
+        for (size_t ti = ch.t0; ti < ch.t0 + ch.nt; ++ti) {
+            const TicketView &t = views[ti];
+            const size_t f0 = t.first_chain / nch;
+            symaccel_flac_md5_job j{};
+            j.rows = reinterpret_cast<const int32_t *>(d_rows + (size_t)t.first_chain * pitch_bytes);
+            j.frames = reinterpret_cast<const symaccel_flac_md5_frame *>(d_frames) + f0;
+            j.state = t.status == SYMACCEL_OK ? reinterpret_cast<symaccel_md5_state *>(d_state_in) + f0 : nullptr;
+            j.checkpoints = reinterpret_cast<symaccel_md5_state *>(d_state_out) + f0;
+            j.row_pitch = pitch_bytes / 4;
+            j.n_frames = t.n_chains / nch;
+            j.nch = (uint8_t)nch;
+            j.bytes_per_sample = 0;  // (every frame names its own: check_flac)
+            h_jobs[ti] = j;
+        }
+        pw.add(h_jobs + ch.t0, d_jobs + ch.t0, ch.nt * sizeof(symaccel_flac_md5_job));
+    }
+    int run(symaccel_ctx *ctx, const Chunk &ch, bool finish, uint32_t shift) const { return launch_flac_md5(ctx, d_jobs + ch.t0, ch.nt, finish, shift); }
 };
 
 // ------------------------------------------------------------------------------------------------ AAC_DECODE

@@ -1113,6 +1113,15 @@ int symaccel_flac_md5_device(symaccel_ctx *ctx, const symaccel_flac_md5_job *d_j
     return launch_flac_md5(ctx, d_jobs, n_jobs);
 }
 
+int symaccel_flac_md5_finish_device(symaccel_ctx *ctx, const symaccel_flac_md5_job *d_jobs, size_t n_jobs, uint32_t out_shift) {
+    if (!ctx || out_shift > 31) return SYMACCEL_ERR_INVALID_ARG;
+    if (n_jobs == 0) return SYMACCEL_OK;
+    if (!d_jobs) return SYMACCEL_ERR_INVALID_ARG;
+    DeviceGuard dev(ctx);
+    if (!dev.ok()) return dev.status();
+    return launch_flac_md5(ctx, d_jobs, n_jobs, true, out_shift);
+}
+
 int symaccel_flac_md5(symaccel_ctx *ctx, const int32_t *h_rows, size_t row_pitch, const symaccel_flac_md5_frame *h_frames, size_t n_frames,
                       int nch, int bytes_per_sample, symaccel_md5_state *h_state_io, symaccel_md5_state *h_checkpoints) {
     if (!ctx || !h_state_io || nch < 1 || nch > 8 || bytes_per_sample < 0 || bytes_per_sample > 4 || n_frames > 0xffffffffu)

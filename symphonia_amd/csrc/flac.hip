@@ -387,6 +387,10 @@ __global__ void flac_decorrelate_kernel(const uint8_t *__restrict__ mode, int32_
 // buffer in LDS behind the bytes still pending from before.  Then the chain runs over every complete 64-byte block of the buffer on
 // wave-uniform values (the 16 words read from LDS and made scalar: the arithmetic goes to the scalar unit), and the incomplete rest
 // moves to the front.  The state after every frame is written out as a checkpoint.
+// FINISH: the wavefront holds the frame's samples decorrelated and not yet shifted -- what the reference hashes and then left-justifies
+// (decoder.rs:231-242) -- so each lane also stores `x[c] << out_shift` back over the word it read (one coalesced 256-byte store per row per
+// chunk, issued before the chain runs over the chunk's blocks): the plane is final PCM when the launch ends, with no pass of its own.
+// Words past block_len are left as they are.
 constexpr int kMd5Chunk = 64;                                 // sample-frames per chunk, one per lane
 constexpr int kMd5BufBytes = 64 + kMd5Chunk * 8 * 4 + 64;     // pending (< 64) + one chunk of 8 channels x 4 bytes, rounded up
 
@@ -430,7 +434,8 @@ __device__ __forceinline__ void md5_store(const uint32_t (&abcd)[4], uint64_t le
     }
 }
 
-__global__ __launch_bounds__(64) void flac_md5_kernel(const symaccel_flac_md5_job *__restrict__ jobs) {
+template <bool FINISH>
+__global__ __launch_bounds__(64) void flac_md5_kernel(const symaccel_flac_md5_job *__restrict__ jobs, uint32_t out_shift) {
     __shared__ __attribute__((aligned(16))) uint8_t buf[kMd5BufBytes];
     const int lane = (int)threadIdx.x;
     const symaccel_flac_md5_job job = jobs[blockIdx.x];
@@ -473,6 +478,12 @@ __global__ __launch_bounds__(64) void flac_md5_kernel(const symaccel_flac_md5_jo
                 const unsigned cnt = min((unsigned)kMd5Chunk, n - i0);
                 if ((unsigned)lane < cnt) {
                     if (mode) md5_decorrelate(mode, x[0], x[1]);
+                    if (FINISH) {  // (wrapping, as flac_decorrelate_kernel)
+                        int32_t *w0 = const_cast<int32_t *>(row0) + i0 + (unsigned)lane;
+#pragma unroll
+                        for (int c = 0; c < 8; ++c)
+                            if ((unsigned)c < nch) w0[(size_t)c * job.row_pitch] = (int32_t)((uint32_t)x[c] << out_shift);
+                    }
                     uint8_t *p = buf + pend + (unsigned)lane * stride;
 #pragma unroll
                     for (int c = 0; c < 8; ++c)
@@ -508,9 +519,11 @@ __global__ __launch_bounds__(64) void flac_md5_kernel(const symaccel_flac_md5_jo
 
 }  // namespace
 
-int launch_flac_md5(symaccel_ctx *ctx, const symaccel_flac_md5_job *d_jobs, size_t n_jobs) {
-    if (n_jobs > 0x7fffffffu) return SYMACCEL_ERR_INVALID_ARG;
-    hipLaunchKernelGGL(flac_md5_kernel, dim3((unsigned)n_jobs), dim3(64), 0, ctx->stream, d_jobs);  // one wavefront per job
+int launch_flac_md5(symaccel_ctx *ctx, const symaccel_flac_md5_job *d_jobs, size_t n_jobs, bool finish, uint32_t out_shift) {
+    if (n_jobs > 0x7fffffffu || out_shift > 31) return SYMACCEL_ERR_INVALID_ARG;
+    const dim3 g((unsigned)n_jobs), b(64);  // one wavefront per job
+    if (finish) hipLaunchKernelGGL(flac_md5_kernel<true>, g, b, 0, ctx->stream, d_jobs, out_shift);
+    else hipLaunchKernelGGL(flac_md5_kernel<false>, g, b, 0, ctx->stream, d_jobs, 0u);
     SYM_GPU(ctx, hipGetLastError());
     return SYMACCEL_OK;
 }

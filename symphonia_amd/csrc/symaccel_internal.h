@@ -454,6 +454,6 @@ int launch_probe_copy(symaccel_ctx *ctx, const void *d_src, void *d_dst, size_t 
 int launch_flac_decorrelate(symaccel_ctx *ctx, const uint8_t *d_mode, int32_t *d_ch0, int32_t *d_ch1,
                             size_t n_pairs, size_t blocksize, uint32_t out_shift);
 // flac.hip: STREAMINFO MD5, one lane per job (d_jobs and everything it points to on the device)
-int launch_flac_md5(symaccel_ctx *ctx, const symaccel_flac_md5_job *d_jobs, size_t n_jobs);
+int launch_flac_md5(symaccel_ctx *ctx, const symaccel_flac_md5_job *d_jobs, size_t n_jobs, bool finish = false, uint32_t out_shift = 0);
 
 }  // namespace symaccel

@@ -9,12 +9,14 @@
 // peek that copies the next packet out of a small pool (a parser writes its output somewhere too).  Nothing here links the
 // oracle: bench.py times the CPU port beside this with its own harness.  One JSON line on stdout.
 //
-//   decoders_bench --codec aac|aacd|mp3|mp3h|vorbis|flac --streams S --lookahead L --packets P --threads T [--per-stream] [--direct] [--in-phase] [--flush-mb M] [--lanes N] [--via-registry] [--out-format f32|s16|s24|u8|f32i]
+//   decoders_bench --codec aac|aacd|mp3|mp3h|vorbis|flac --streams S --lookahead L --packets P --threads T [--per-stream] [--direct] [--in-phase] [--flush-mb M] [--lanes N] [--via-registry] [--out-format f32|s16|s24|u8|f32i] [--verify]
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <random>
@@ -34,6 +36,9 @@ struct Args {
     std::string codec = "aac";
     size_t streams = 64, lookahead = 64, packets = 512, threads = 1, flush_mb = 0, warm = 0, lanes = 0;
     bool per_stream = false, direct = false, in_phase = false, via_registry = false;
+    // --verify (FLAC): every decoder hashes what it decodes (AudioDecoderOptions::verify, the STREAMINFO MD5) and every stream carries its true
+    // digest; a stream whose finalize() is not Some(true) at the end is a failure
+    bool verify = false;
     // --out-format: what the decoders deliver.  f32 (the default) = the planes as they are (planar f32; FLAC: left-justified i32) -- the
     // path without a conversion; s16 / s24 / u8 / f32i = interleaved samples of that format, converted in the batcher's scatter
     // (LookaheadDecoder::set_output; f32i: f32, interleaved)
@@ -225,6 +230,46 @@ Vorbis::Params params<Vorbis>() { return Vorbis::Params{8, 8, 11}; }
 template <>
 Flac::Params params<Flac>() { return Flac::Params{2, 24, 4096}; }
 
+// --verify: the digest a FLAC stream of `count[s]` packets pool[(i + salt[s]) % kPool], i = 0 .. count[s], must have.  The bytes validate.rs
+// hashes are the low three bytes of every decorrelated 24-bit sample, which are the upper three of the left-justified sample the decoder
+// delivers: the pool is decoded once by a decoder that does NOT verify, and the chains are hashed on the host (symaccel_md5_update) -- one
+// chain per distinct salt, read off at every length a stream has, the chains spread over a few threads.
+using Digest = std::array<uint8_t, 16>;
+template <class Decoder>
+std::vector<Digest> true_digests(Decoder &plain, const std::vector<Flac::Packet> &pool, const std::vector<size_t> &salt, const std::vector<size_t> &count) {
+    std::vector<std::vector<uint8_t>> hashed(kPool);
+    for (size_t k = 0; k < kPool; ++k) {
+        Flac::Packet p = pool[k];
+        p.ts = k;
+        const auto &buf = plain.decode(p);
+        hashed[k].resize(buf.frames * 2 * 3);
+        for (size_t f = 0; f < buf.frames; ++f)
+            for (size_t c = 0; c < 2; ++c) std::memcpy(hashed[k].data() + (f * 2 + c) * 3, reinterpret_cast<const uint8_t *>(buf.planes[c] + f) + 1, 3);
+    }
+    std::map<size_t, std::map<size_t, Digest>> chains;  // salt % kPool -> length -> digest
+    for (size_t s = 0; s < salt.size(); ++s) chains[salt[s] % kPool][count[s]] = Digest{};
+    std::vector<std::pair<size_t, std::map<size_t, Digest> *>> work;
+    for (auto &c : chains) work.push_back({c.first, &c.second});
+    std::atomic<size_t> next{0};
+    std::vector<std::thread> ths;
+    for (size_t t = 0; t < std::min<size_t>(8, work.size()); ++t)
+        ths.emplace_back([&]() {
+            for (size_t w = next++; w < work.size(); w = next++) {
+                symaccel_md5_state st;
+                symaccel_md5_init(&st);
+                size_t done = 0;
+                for (auto &want : *work[w].second) {  // (ascending lengths)
+                    for (; done < want.first; ++done) symaccel_md5_update(&st, hashed[(done + work[w].first) % kPool].data(), hashed[(done + work[w].first) % kPool].size());
+                    symaccel_md5_digest(&st, want.second.data());
+                }
+            }
+        });
+    for (auto &th : ths) th.join();
+    std::vector<Digest> out(salt.size());
+    for (size_t s = 0; s < salt.size(); ++s) out[s] = chains[salt[s] % kPool][count[s]];
+    return out;
+}
+
 template <class Codec>
 int run(const Args &a, const char *codec_name, size_t frames_per_packet, size_t bytes_in_per_packet) {
     using Packet = typename Codec::Packet;
@@ -257,14 +302,37 @@ int run(const Args &a, const char *codec_name, size_t frames_per_packet, size_t 
     };
     std::vector<std::unique_ptr<Stream>> streams(a.streams);
     const size_t total = a.warm + a.packets;
+    // streams do not start together in a service: stream s of a thread's S / T streams is (s / T) * L / (S / T) packets ahead of the
+    // first, so that the batches of a thread's streams end at different times (--in-phase: every stream at the same packet)
+    const size_t per_thread = std::max<size_t>(1, (a.streams + std::min(a.threads, a.streams) - 1) / std::min(a.threads, a.streams));
+    auto lead_of = [&](size_t s) { return a.in_phase ? (size_t)0 : (s / std::min(a.threads, a.streams)) * a.lookahead / per_thread; };
+    std::vector<typename Codec::Params> stream_params(a.streams, params<Codec>());
+    if (a.verify) {
+        if constexpr (std::is_same<Codec, Flac>::value) {
+            if (a.format() != SampleFormat::Native) throw std::invalid_argument("--verify: the planes are hashed as they are decoded (no --out-format)");
+            std::vector<size_t> salt(a.streams), count(a.streams);
+            for (size_t s = 0; s < a.streams; ++s) salt[s] = s * 7, count[s] = total + lead_of(s);  // (what the two phases below decode of stream s)
+            std::vector<Digest> want;
+            if (batcher) {
+                Decoder plain(*batcher, params<Codec>(), kPool, nullptr);
+                want = true_digests(plain, pool, salt, count);
+            } else {
+                Decoder plain(ctx, params<Codec>(), kPool, nullptr);
+                want = true_digests(plain, pool, salt, count);
+            }
+            for (size_t s = 0; s < a.streams; ++s) {
+                stream_params[s].verify = true;
+                stream_params[s].expected_md5 = want[s];
+            }
+        } else {
+            throw std::invalid_argument("--verify: FLAC is the codec with a checksum");
+        }
+    }
     for (size_t s = 0; s < a.streams; ++s) {
         streams[s].reset(new Stream());
         Stream *st = streams[s].get();
         st->salt = s * 7;
-        // streams do not start together in a service: stream s of a thread's S / T streams is (s / T) * L / (S / T) packets ahead of the
-        // first, so that the batches of a thread's streams end at different times (--in-phase: every stream at the same packet)
-        const size_t per_thread = std::max<size_t>(1, (a.streams + std::min(a.threads, a.streams) - 1) / std::min(a.threads, a.streams));
-        st->lead = a.in_phase ? 0 : (s / std::min(a.threads, a.streams)) * a.lookahead / per_thread;
+        st->lead = lead_of(s);
         st->limit = total + st->lead + 2 * a.lookahead;  // (no stream ends inside the timed region: a tail batch is a shape of its own)
         auto peek = [st, &pool]() -> std::optional<Packet> {
             if (st->cursor >= st->limit) return std::nullopt;
@@ -282,18 +350,18 @@ int run(const Args &a, const char *codec_name, size_t frames_per_packet, size_t 
                     return st->cursor++;
                 };
                 if (a.via_registry)
-                    st->dec = registry.make_audio_decoder<Codec>(params<Codec>(), AudioDecoderOptions{false, a.lookahead}, d);
+                    st->dec = registry.make_audio_decoder<Codec>(stream_params[s], AudioDecoderOptions{a.verify, a.lookahead}, d);
                 else
-                    st->dec.reset(new Decoder(*batcher, params<Codec>(), a.lookahead, d));
+                    st->dec.reset(new Decoder(*batcher, stream_params[s], a.lookahead, d));
             } else {
                 throw std::invalid_argument("--direct: this codec's layout depends on the packets (use the peek form)");
             }
         } else if (a.via_registry)
-            st->dec = registry.make_audio_decoder<Codec>(params<Codec>(), AudioDecoderOptions{false, a.lookahead}, peek);
+            st->dec = registry.make_audio_decoder<Codec>(stream_params[s], AudioDecoderOptions{a.verify, a.lookahead}, peek);
         else if (batcher)
-            st->dec.reset(new Decoder(*batcher, params<Codec>(), a.lookahead, peek));
+            st->dec.reset(new Decoder(*batcher, stream_params[s], a.lookahead, peek));
         else
-            st->dec.reset(new Decoder(ctx, params<Codec>(), a.lookahead, peek));
+            st->dec.reset(new Decoder(ctx, stream_params[s], a.lookahead, peek));
         if (a.format() != SampleFormat::Native) st->dec->set_output(a.format(), true);  // (needs the batcher: throws with --per-stream)
     }
     std::mutex ctx_mu;  // per-stream mode: one context, externally synchronised
@@ -353,15 +421,20 @@ int run(const Args &a, const char *codec_name, size_t frames_per_packet, size_t 
     const double secs = std::chrono::duration<double>(Clock::now() - t0).count();
     symaccel_batcher_stats s1{};
     if (batcher) s1 = batcher->stats();
-    size_t batches = 0;
+    size_t batches = 0, verified = 0;
     for (auto &st : streams) batches += st->dec->batches_run();
+    for (auto &st : streams) verified += st->dec->finalize().verify_ok.value_or(false) ? 1 : 0;
+    if (a.verify && verified != a.streams) {
+        std::fprintf(stderr, "--verify: %zu of %zu streams have their digest\n", verified, a.streams);
+        failures += 1;
+    }
     streams.clear();
     const double n = (double)a.streams * (double)a.packets;
     std::printf("{\"codec\": \"%s\", \"mode\": \"%s\", \"direct\": %s, \"in_phase\": %s, \"streams\": %zu, \"lookahead\": %zu, \"threads\": %zu, \"packets\": %.0f, \"seconds\": %.6f, "
                 "\"packets_per_s\": %.1f, \"frames_per_packet\": %zu, \"host_bytes_in_per_packet\": %zu, \"host_bytes_out_per_packet\": %zu, "
                 "\"GBps_each_way\": [%.3f, %.3f], \"decoder_batches\": %zu, \"launches\": %llu, \"kernel_launches\": %llu, \"max_chains_per_launch\": %llu, "
                 "\"staging_bytes\": %llu, \"staging_grew_bytes\": %llu, \"slots_peak\": [%llu, %llu], \"lanes\": %llu, \"mutex_wait_ms\": %.3f, \"mutex_contended\": %llu, \"launch_host_ms\": %.3f, \"launch_api_ms\": %.3f, \"lane_wait_ms\": %.3f, \"group_allocs\": %llu, \"blocks\": %llu, \"flag_wait_ms\": %.3f, \"commit_to_launch_ms_per_submission\": %.3f, \"waits\": %llu, \"waits_blocked\": %llu, \"launch_to_done_ms\": %.3f, "
-                "\"failed_tickets\": %llu, \"failures\": %zu, \"checksum\": %llu, \"out_format\": \"%s\", \"flag_wait_ns\": %llu}\n",
+                "\"failed_tickets\": %llu, \"failures\": %zu, \"checksum\": %llu, \"out_format\": \"%s\", \"flag_wait_ns\": %llu, \"verify\": %s, \"streams_verified\": %zu}\n",
                 codec_name, a.via_registry ? "registry" : (batcher ? "batcher" : "per-stream"), a.direct ? "true" : "false", a.in_phase ? "true" : "false", a.streams, a.lookahead, std::min(a.threads, a.streams), n, secs, n / secs, frames_per_packet,
                 bytes_in_per_packet, frames_per_packet * params<Codec>().channels * out_sample_bytes, n * bytes_in_per_packet / secs / 1e9,
                 n * frames_per_packet * params<Codec>().channels * out_sample_bytes / secs / 1e9, batches,
@@ -371,7 +444,7 @@ int run(const Args &a, const char *codec_name, size_t frames_per_packet, size_t 
                 (double)(s1.launch_host_ns - s0.launch_host_ns) / 1e6, (double)(s1.launch_api_ns - s0.launch_api_ns) / 1e6,
                 (double)(s1.lane_wait_ns - s0.lane_wait_ns) / 1e6, (unsigned long long)(s1.group_allocs - s0.group_allocs), (unsigned long long)s1.blocks, (double)(s1.flag_wait_ns - s0.flag_wait_ns) / 1e6, (double)(s1.commit_to_launch_ns - s0.commit_to_launch_ns) / 1e6 / (double)std::max<uint64_t>(1, s1.submissions - s0.submissions), (unsigned long long)(s1.waits - s0.waits), (unsigned long long)(s1.waits_blocked - s0.waits_blocked), (double)(s1.launch_to_done_ns - s0.launch_to_done_ns) / 1e6 / (double)std::max<uint64_t>(1, s1.launches_timed - s0.launches_timed),
                 (unsigned long long)(s1.failed_tickets - s0.failed_tickets), failures.load(),
-                (unsigned long long)checksum.load(), a.out_format.c_str(), (unsigned long long)(s1.flag_wait_ns - s0.flag_wait_ns));
+                (unsigned long long)checksum.load(), a.out_format.c_str(), (unsigned long long)(s1.flag_wait_ns - s0.flag_wait_ns), a.verify ? "true" : "false", verified);
     return failures.load() ? 1 : 0;
 }
 
@@ -394,6 +467,7 @@ int main(int argc, char **argv) {
         else if (k == "--direct") a.direct = true;
         else if (k == "--in-phase") a.in_phase = true;
         else if (k == "--via-registry") a.via_registry = true;
+        else if (k == "--verify") a.verify = true;
         else if (k == "--out-format" && i + 1 < argc) a.out_format = argv[++i];
         else {
             std::fprintf(stderr, "unknown argument %s\n", k.c_str());

@@ -5,7 +5,8 @@ S streams, each a batch of F frames of 4096-sample 16-bit stereo (what `decoders
     python tools/flac_md5_time.py [--frames F] [--streams 1,16,256,1024]
 
 Prints one JSON line per S: ms per MD5 launch, the restore of the same subframes (order-8 LPC, padded rows as the batcher lays them
-out), the MD5 / restore ratio, and MB/s hashed per stream and in all.  Every stream's digest is checked against hashlib."""
+out), the MD5 / restore ratio, MB/s hashed per stream and in all, and the finishing form (symaccel_flac_md5_finish_device) against
+restore + MD5 + decorrelate as three launches.  Every stream's digest is checked against hashlib."""
 import argparse
 import hashlib
 import json
@@ -85,8 +86,18 @@ def main():
         fp = sa.FlacPredictor(ctx)
         work = rows.clone()
         restore_ms = timed(lambda: fp.restore_strided(work, desc, co, bs), a.reps)
+        # the finishing form (symaccel_flac_md5_finish_device: the MD5 walk also leaves the planes decorrelated and << 16) against what it
+        # replaces on the same frames: restore + MD5 + decorrelate as three launches (the decorrelate over compact planes of the same size)
+        ch0 = torch.randint(-(1 << 15), 1 << 15, (S * F, bs), generator=g, device="cuda", dtype=torch.int32)
+        ch1 = ch0.clone()
+        modes = torch.from_numpy((np.arange(S * F) % 4).astype(np.uint8)).cuda()
+        decor_ms = timed(lambda: fp.decorrelate(modes, ch0, ch1, bs, 16), a.reps)
+        finish_ms = timed(lambda: sa.flac_md5_finish_device(ctx, d_jobs, 16, S), a.reps)
         hashed = F * bs * nch * nb
         print(json.dumps({"streams": S, "frames_per_stream": F, "md5_ms": round(md5_ms, 4), "restore_ms": round(restore_ms, 4),
+                          "decorrelate_ms": round(decor_ms, 4), "finish_ms": round(finish_ms, 4),
+                          "restore_plus_finish_ms": round(restore_ms + finish_ms, 4), "three_launches_ms": round(restore_ms + md5_ms + decor_ms, 4),
+                          "finish_path_over_three_launches": round((restore_ms + finish_ms) / (restore_ms + md5_ms + decor_ms), 3),
                           "md5_over_restore": round(md5_ms / restore_ms, 3), "us_per_block_per_stream": round(md5_ms * 1e3 / (hashed / 64), 4),
                           "MBps_per_stream": round(hashed / md5_ms / 1e3, 1), "GBps_total": round(S * hashed / md5_ms / 1e6, 2)}), flush=True)
     ctx.close()
