@@ -13,7 +13,7 @@ use symphonia_core::errors::{decode_error, unsupported_error, Result};
 use symphonia_core::packet::PacketRef;
 use symphonia_core::support_audio_codec;
 
-use crate::ctx::{check, place_rows, Context, Pinned, Pool, SlotCycle};
+use crate::ctx::{check, narrow_words, place_rows, Context, Pinned, Pool, SlotCycle};
 use crate::decoder::DecoderBatch;
 use crate::ffi;
 use crate::lookahead::{BatchCodec, Lookahead};
@@ -189,6 +189,9 @@ pub struct AlacBatch {
     // the slot cycle of ctx.rs: what follows the predictor is applied to a batch that came through it in place, in the page-locked slot
     slots: SlotCycle<AlacIndex>,
     buf: AudioBuffer<i32>,
+    // the batches submitted with their words as i16 (every word fits: ctx.rs narrow_words) and as i32
+    narrow_batches: usize,
+    wide_batches: usize,
 }
 
 /// Where `publish` finds a packet in its batch, and what is left to do to it.
@@ -251,7 +254,7 @@ impl BatchCodec for AlacBatch {
         // the predicted element channels: in the batcher's slot (in place: the result plane IS input plane 0), or in this decoder's buffer
         let (ix, slot) = self.slots.parts_mut();
         let words: &mut [i32] = match slot {
-            Some(slot) => slot.input::<i32>(0),
+            Some(slot) => slot.out_mut::<i32>(),
             None => self.words.as_mut_slice(),
         };
         let (n, stride) = (ix.lens[i], ix.stride);
@@ -312,8 +315,19 @@ impl BatchCodec for AlacBatch {
         if k == 0 || stride == 0 {
             return unsupported_error("alac: an empty batch, or empty packets");
         }
-        self.slots.submit(ffi::SYMACCEL_BATCH_ALAC_PREDICT as i32, 0, k * nch, stride, Self::index_of(batch, stride), |slot| {
-            place_rows(slot.input::<i32>(0), batch, nch, stride, 0, |p| p.words.as_slice());
+        // a batch whose every word fits i16 goes up as i16 (the gather of the launch widens it); per batch
+        let packed = if self.slots.narrow_input() { narrow_words(batch, |p| p.words.as_slice()) } else { None };
+        let in_fmt = if packed.is_some() { ffi::SYMACCEL_FMT_S16 as i32 } else { 0 };
+        if packed.is_some() {
+            self.narrow_batches += 1;
+        } else {
+            self.wide_batches += 1;
+        }
+        self.slots.submit_io(ffi::SYMACCEL_BATCH_ALAC_PREDICT as i32, 0, k * nch, stride, in_fmt, Self::index_of(batch, stride), |slot| {
+            match &packed {
+                Some(rows) => place_rows(slot.input::<i16>(0), rows, nch, stride, 0, |r| r.as_slice()),
+                None => place_rows(slot.input::<i32>(0), batch, nch, stride, 0, |p| p.words.as_slice()),
+            }
             place_rows(slot.input::<ffi::SymaccelAlacDesc>(1), batch, nch, 1, NO_DESC, |p| p.desc.as_slice());
             place_rows(slot.input::<i32>(2), batch, nch, 32, 0, |p| p.coeffs.as_slice());
             Ok(())
@@ -349,6 +363,15 @@ crate::hip_decoder!(
 crate::hip_decoder!(@new HipAlacDecoder, crate::frontends::alac_front_end, Box<dyn AlacFrontEnd>);
 
 impl HipAlacDecoder {
+    /// The batches this decoder sent to the batcher with their words as `i16` / as `i32`.
+    pub fn narrow_batches(&self) -> usize {
+        self.batch.narrow_batches
+    }
+
+    pub fn wide_batches(&self) -> usize {
+        self.batch.wide_batches
+    }
+
     pub fn try_new_with_pool(
         _params: &AudioCodecParameters,
         _opts: &AudioDecoderOptions,
@@ -374,6 +397,8 @@ impl HipAlacDecoder {
                 coeffs: vec![0; max_batch * nch * 32],
                 slots: SlotCycle::new(pool, AlacBatch::index_of(&[], max_frames)),
                 buf: AudioBuffer::new(AudioSpec::new(rate, channels), max_frames),
+                narrow_batches: 0,
+                wide_batches: 0,
             },
             la: Lookahead::new(max_batch),
         })

@@ -72,6 +72,9 @@ impl Drop for Context {
 pub struct Pool {
     batcher: *mut ffi::SymaccelBatcher,
     ctx: Context, // (declared after `batcher`: Drop destroys the batcher first, then the field drops the context)
+    /// SYMACCEL_NARROW_INPUT, read once when the pool is made: the FLAC / ALAC decoders send a batch whose every word fits `i16` up as
+    /// `i16` (`symaccel_batcher_reserve_io`).  Off unless the variable is set to something other than 0.
+    narrow: bool,
 }
 
 unsafe impl Send for Pool {}
@@ -104,9 +107,18 @@ impl Pool {
         let mut batcher = ptr::null_mut();
         // SAFETY: valid context, valid out-pointer.
         check(unsafe { ffi::symaccel_batcher_create(ctx.raw(), 0, &mut batcher) }, ctx.raw())?;
-        let pool = Arc::new(Pool { batcher, ctx });
+        let narrow = match std::env::var("SYMACCEL_NARROW_INPUT") {
+            Ok(v) => !v.is_empty() && v != "0",
+            Err(_) => false,
+        };
+        let pool = Arc::new(Pool { batcher, ctx, narrow });
         *slot = Some(pool.clone());
         Ok(pool)
+    }
+
+    /// Do the FLAC / ALAC decoders of this pool narrow their batches (SYMACCEL_NARROW_INPUT at its creation)?
+    pub fn narrow_input(&self) -> bool {
+        self.narrow
     }
 
     pub(crate) fn raw(&self) -> *mut ffi::SymaccelBatcher {
@@ -153,6 +165,13 @@ impl BatchSlot {
         unsafe { std::slice::from_raw_parts(self.raw.out as *const T, self.raw.out_bytes / std::mem::size_of::<T>()) }
     }
 
+    /// The result plane for a codec that finishes a packet in place in it (ALAC).  Not `input(0)`: a slot whose plane 0 went up as
+    /// `i16` (`Pool::reserve_io`) has half as many input bytes as result bytes.
+    pub fn out_mut<T: Copy>(&mut self) -> &mut [T] {
+        // SAFETY: as `out`; exclusively ours until release.
+        unsafe { std::slice::from_raw_parts_mut(self.raw.out as *mut T, self.raw.out_bytes / std::mem::size_of::<T>()) }
+    }
+
     pub fn is_committed(&self) -> bool {
         self.committed
     }
@@ -177,6 +196,12 @@ impl Pool {
 
     /// `symaccel_batcher_reserve`: a slot for `n_chains` chains of `units` frames / granules / blocks / words each.
     pub fn reserve(&self, kind: i32, param: i32, n_chains: usize, units: usize) -> Result<BatchSlot> {
+        self.reserve_io(kind, param, n_chains, units, 0)
+    }
+
+    /// `symaccel_batcher_reserve_io`: `in_fmt` `SYMACCEL_FMT_S16` (FLAC_RESTORE / ALAC_PREDICT) makes input plane 0 a plane of `i16`
+    /// words, widened by the gather of the launch; 0 is `reserve`.
+    pub fn reserve_io(&self, kind: i32, param: i32, n_chains: usize, units: usize, in_fmt: i32) -> Result<BatchSlot> {
         let mut raw = ffi::SymaccelBatchSlot {
             input: [ptr::null_mut(); 6],
             state: [ptr::null_mut(); 3],
@@ -187,7 +212,13 @@ impl Pool {
         };
         let mut ticket = 0u64;
         // SAFETY: a live batcher, valid out-pointers.
-        self.check(unsafe { ffi::symaccel_batcher_reserve(self.batcher, kind, param, n_chains, units, &mut raw, &mut ticket) })?;
+        self.check(unsafe {
+            if in_fmt == 0 {
+                ffi::symaccel_batcher_reserve(self.batcher, kind, param, n_chains, units, &mut raw, &mut ticket)
+            } else {
+                ffi::symaccel_batcher_reserve_io(self.batcher, kind, param, n_chains, units, in_fmt, 0, 0, &mut raw, &mut ticket)
+            }
+        })?;
         Ok(BatchSlot { raw, ticket, committed: false })
     }
 
@@ -328,13 +359,26 @@ impl<M> SlotCycle<M> {
     /// `reserve` -> `fill` -> `commit`.  Refused without a pool and while a batch is submitted.  Whatever fails after `reserve`, the
     /// slot goes back and nothing is pending.
     pub fn submit<F: FnOnce(&mut BatchSlot) -> Result<()>>(&mut self, kind: i32, param: i32, n_chains: usize, units: usize, index: M, fill: F) -> Result<()> {
+        self.submit_io(kind, param, n_chains, units, 0, index, fill)
+    }
+
+    /// Does the pool narrow (`Pool::narrow_input`)?  `false` without a pool.
+    pub fn narrow_input(&self) -> bool {
+        match &self.pool {
+            Some(pool) => pool.narrow_input(),
+            None => false,
+        }
+    }
+
+    /// `submit` with an input format (`Pool::reserve_io`): `fill` writes plane 0 as `i16` words when `in_fmt` is `SYMACCEL_FMT_S16`.
+    pub fn submit_io<F: FnOnce(&mut BatchSlot) -> Result<()>>(&mut self, kind: i32, param: i32, n_chains: usize, units: usize, in_fmt: i32, index: M, fill: F) -> Result<()> {
         let Some(pool) = self.pool.clone() else {
             return unsupported_error("no batcher");
         };
         if self.next.is_some() {
             return unsupported_error("one batch at a time");
         }
-        let mut slot = pool.reserve(kind, param, n_chains, units)?;
+        let mut slot = pool.reserve_io(kind, param, n_chains, units, in_fmt)?;
         let filled = match fill(&mut slot) {
             Ok(()) => pool.commit(&mut slot),
             Err(e) => Err(e),
@@ -411,6 +455,22 @@ pub(crate) fn place_rows<P, T: Copy>(dst: &mut [T], batch: &[P], nch: usize, pit
             dst[at + w..at + pitch].fill(zero);
         }
     }
+}
+
+/// The words of every packet of a batch as `i16`, if every one of them fits: one `symaccel_host_narrow_s16` per packet decides and packs
+/// in the same pass.  `None` as soon as a packet has a word that does not fit (a side channel's 17-bit warm-up): the batch goes up wide.
+pub(crate) fn narrow_words<P>(batch: &[P], words: impl Fn(&P) -> &[i32]) -> Option<Vec<Vec<i16>>> {
+    let mut packed: Vec<Vec<i16>> = Vec::with_capacity(batch.len());
+    for p in batch.iter() {
+        let src = words(p);
+        let mut dst = vec![0i16; src.len()];
+        // SAFETY: `src` and `dst` hold `src.len()` words each; plain host code.
+        if unsafe { ffi::symaccel_host_narrow_s16(src.as_ptr(), dst.as_mut_ptr(), src.len()) } == 0 {
+            return None;
+        }
+        packed.push(dst);
+    }
+    Some(packed)
 }
 
 /// Page-locked host memory (symaccel_host_alloc): what the staged host entry points need to overlap H2D, kernels and D2H.

@@ -11,7 +11,7 @@ use symphonia_core::errors::{decode_error, unsupported_error, Result};
 use symphonia_core::packet::PacketRef;
 use symphonia_core::support_audio_codec;
 
-use crate::ctx::{check, place_rows, Context, Pinned, Pool, SlotCycle};
+use crate::ctx::{check, narrow_words, place_rows, Context, Pinned, Pool, SlotCycle};
 use crate::decoder::DecoderBatch;
 use crate::ffi;
 use crate::lookahead::{BatchCodec, Lookahead};
@@ -191,6 +191,9 @@ pub struct FlacBatch {
     published: ffi::SymaccelMd5State,
     chain_end: ffi::SymaccelMd5State,
     cps: Vec<ffi::SymaccelMd5State>,  // the state after every packet of a batch transformed here (a slot carries its own)
+    // the batches submitted with their words as i16 (every word fits: ctx.rs narrow_words) and as i32
+    narrow_batches: usize,
+    wide_batches: usize,
 }
 
 /// Where `publish` finds a packet in its batch.
@@ -367,8 +370,19 @@ impl BatchCodec for FlacBatch {
         // verifying: the kind's verify form -- a frame record per packet and the state the chain starts from, entry 0 of the state plane
         let (verify, start) = (self.verify, self.chain_end);
         let param = if verify { 0x200 | ((nch as i32 - 1) << 12) } else { 0 };
-        self.slots.submit(ffi::SYMACCEL_BATCH_FLAC_RESTORE as i32, param, k * nch, stride, Self::index_of(batch, nch, stride), |slot| {
-            place_rows(slot.input::<i32>(0), batch, nch, stride, 0, |p| p.words.as_slice());
+        // a batch whose every warm-up sample and residual fits i16 goes up as i16 (the gather of the launch widens it); per batch
+        let packed = if self.slots.narrow_input() { narrow_words(batch, |p| p.words.as_slice()) } else { None };
+        let in_fmt = if packed.is_some() { ffi::SYMACCEL_FMT_S16 as i32 } else { 0 };
+        if packed.is_some() {
+            self.narrow_batches += 1;
+        } else {
+            self.wide_batches += 1;
+        }
+        self.slots.submit_io(ffi::SYMACCEL_BATCH_FLAC_RESTORE as i32, param, k * nch, stride, in_fmt, Self::index_of(batch, nch, stride), |slot| {
+            match &packed {
+                Some(rows) => place_rows(slot.input::<i16>(0), rows, nch, stride, 0, |r| r.as_slice()),
+                None => place_rows(slot.input::<i32>(0), batch, nch, stride, 0, |p| p.words.as_slice()),
+            }
             place_rows(slot.input::<ffi::SymaccelFlacDesc>(1), batch, nch, 1, NO_DESC, |p| p.desc.as_slice());
             place_rows(slot.input::<i32>(2), batch, nch, 32, 0, |p| p.coeffs.as_slice());
             if verify {
@@ -436,6 +450,15 @@ crate::hip_decoder!(
 crate::hip_decoder!(@new HipFlacDecoder, crate::frontends::flac_front_end, Box<dyn FlacFrontEnd>);
 
 impl HipFlacDecoder {
+    /// The batches this decoder sent to the batcher with their words as `i16` / as `i32`.
+    pub fn narrow_batches(&self) -> usize {
+        self.batch.narrow_batches
+    }
+
+    pub fn wide_batches(&self) -> usize {
+        self.batch.wide_batches
+    }
+
     pub fn try_new_with_pool(
         _params: &AudioCodecParameters,
         opts: &AudioDecoderOptions,
@@ -476,6 +499,8 @@ impl HipFlacDecoder {
                 published: md5_initial(),
                 chain_end: md5_initial(),
                 cps: Vec::new(),
+                narrow_batches: 0,
+                wide_batches: 0,
             },
             la: Lookahead::new(max_batch),
         })

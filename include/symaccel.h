@@ -52,7 +52,7 @@
 extern "C" {
 #endif
 
-#define SYMACCEL_ABI_VERSION 8 /* 2: *_pp_device entry points, per-block status arrays, lookahead staging; 3: multi-GPU, probe; 4: mp3_decode_*device, vorbis floor_y; 5: aac_decode_pipelined, aac_joint_stereo_list, vorbis_decode; 6: batcher; 7: batch kinds for Vorbis from posts, FLAC and ALAC (symaccel_batch_slot has six input planes), lanes, per-ticket status; 8: *_strided_device (padded row pitch for the FLAC / ALAC planes), symaccel_row_stride; additions within 8: symaccel_md5_*, symaccel_flac_md5(_device) (STREAMINFO MD5), SYMACCEL_FMT_*, symaccel_sample_bytes, symaccel_pcm_convert(_device), symaccel_batcher_reserve_fmt / _submit_fmt, symaccel_adpcm_*, symaccel_mpa12_* (Layer I / II from sample codes) */
+#define SYMACCEL_ABI_VERSION 8 /* 2: *_pp_device entry points, per-block status arrays, lookahead staging; 3: multi-GPU, probe; 4: mp3_decode_*device, vorbis floor_y; 5: aac_decode_pipelined, aac_joint_stereo_list, vorbis_decode; 6: batcher; 7: batch kinds for Vorbis from posts, FLAC and ALAC (symaccel_batch_slot has six input planes), lanes, per-ticket status; 8: *_strided_device (padded row pitch for the FLAC / ALAC planes), symaccel_row_stride; additions within 8: symaccel_md5_*, symaccel_flac_md5(_device) (STREAMINFO MD5), SYMACCEL_FMT_*, symaccel_sample_bytes, symaccel_pcm_convert(_device), symaccel_batcher_reserve_fmt / _submit_fmt, symaccel_adpcm_*, symaccel_mpa12_* (Layer I / II from sample codes), symaccel_batcher_reserve_io / _submit_io and symaccel_host_narrow_s16 (FLAC / ALAC input as int16_t) */
 
 typedef enum symaccel_status {
     SYMACCEL_OK = 0,
@@ -1041,6 +1041,24 @@ int symaccel_batcher_reserve_fmt(symaccel_batcher *b, int kind, int param, size_
                                  int channels, symaccel_batch_slot *slot, uint64_t *ticket);
 int symaccel_batcher_submit_fmt(symaccel_batcher *b, int kind, int param, size_t n_chains, size_t units_per_chain, const void **input,
                                 void **state_io, void *out, int out_fmt, int channels, uint64_t *ticket); /* input[6], state_io[3] */
+/* reserve_fmt() / submit_fmt() with an INPUT format: the mirror image of the converting scatter, a widening gather.  in_fmt 0 is
+ * reserve_fmt() / submit_fmt(), bit for bit.  in_fmt SYMACCEL_FMT_S16 -- FLAC_RESTORE and ALAC_PREDICT only, in every param form of the two
+ * (the verify forms included); any other kind or format: SYMACCEL_ERR_INVALID_ARG -- hands plane 0 over as int16_t: slot.input[0] takes
+ * n_chains * units_per_chain int16_t words, rows back to back, slot.input_bytes[0] says so, and the gather of the launch sign-extends them into
+ * the int32_t device plane; every kernel behind it runs as for a wide submission, so the results are those of the same words sent wide.  What
+ * crosses the link upwards is half the bytes.  slot.out == slot.input[0] still (the region keeps the native plane's size, and a ticket's
+ * gather is complete before its scatter); slot.out_bytes is what it is without an input format.  The bytes of the region behind
+ * input_bytes[0] are not read.  submit_io() takes the narrow plane from input[0].  Submissions of either input format share the groups and
+ * launches of their (kind, param, units_per_chain), and a group is cut into the chunks it would be cut into if every submission were wide.
+ * The library itself never chooses the format.  The decoders above it (C++ codecs::Flac, the Rust shim's FLAC and ALAC decoders) send a
+ * batch narrow when every word of it fits and SYMACCEL_NARROW_INPUT=1 was set when their batcher was made; otherwise wide. */
+int symaccel_batcher_reserve_io(symaccel_batcher *b, int kind, int param, size_t n_chains, size_t units_per_chain, int in_fmt, int out_fmt,
+                                int channels, symaccel_batch_slot *slot, uint64_t *ticket);
+int symaccel_batcher_submit_io(symaccel_batcher *b, int kind, int param, size_t n_chains, size_t units_per_chain, const void **input,
+                               void **state_io, void *out, int in_fmt, int out_fmt, int channels, uint64_t *ticket); /* input[6], state_io[3] */
+/* Plain host code for the front ends that decide and pack in one pass: writes (int16_t)src[i] to dst[i] for all n words and returns 1 if
+ * every word fits int16_t, 0 if some word does not (dst is then unspecified).  n == 0: 1. */
+int symaccel_host_narrow_s16(const int32_t *src, int16_t *dst, size_t n);
 /* submit() with the argument lists of the entry points the kinds stand for (symaccel_aac_synth, symaccel_mp3_synth,
  * symaccel_mp3_decode_pipelined for one stream: n_chains 1, or 2 = one channel pair with st_desc[granule]; st_desc may be NULL for 1) */
 int symaccel_batcher_submit_aac_synth(symaccel_batcher *b, const float *coeffs, const uint8_t *side, float *delay_io, float *pcm,

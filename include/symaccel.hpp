@@ -29,6 +29,7 @@
 #include <complex>
 #include <functional>
 #include <cstdint>
+#include <cstdlib>
 #include <memory>
 #include <mutex>
 #include <optional>
@@ -130,7 +131,10 @@ private:
 // process.  Decoders submit their look-ahead batches; one launch per (kind, units) group serves all of them.  Thread-safe.
 class Batcher {
 public:
-    explicit Batcher(Context &ctx, std::size_t flush_bytes = 0) : ctx_(ctx) { check(symaccel_batcher_create(ctx.raw(), flush_bytes, &b_), ctx.raw()); }
+    explicit Batcher(Context &ctx, std::size_t flush_bytes = 0) : ctx_(ctx) {
+        check(symaccel_batcher_create(ctx.raw(), flush_bytes, &b_), ctx.raw());
+        if (const char *e = std::getenv("SYMACCEL_NARROW_INPUT")) narrow_input_ = std::atoi(e) != 0;  // (read once, like the library's own batcher knobs)
+    }
     ~Batcher() {
         if (b_) symaccel_batcher_destroy(b_);
     }
@@ -145,6 +149,16 @@ public:
         check(symaccel_batcher_get_stats(b_, &s), ctx_.raw());
         return s;
     }
+    // symaccel_batcher_reserve_io: a slot whose plane 0 takes int16_t words (in_fmt SYMACCEL_FMT_S16; FLAC_RESTORE / ALAC_PREDICT), widened in
+    // the gather of the launch; in_fmt 0 = the native planes.  out_fmt / channels as symaccel_batcher_reserve_fmt takes them (0 = native).
+    void reserve_io(int kind, int param, std::size_t n_chains, std::size_t units_per_chain, int in_fmt, int out_fmt, int channels, symaccel_batch_slot *slot,
+                    std::uint64_t *ticket) {
+        check(symaccel_batcher_reserve_io(b_, kind, param, n_chains, units_per_chain, in_fmt, out_fmt, channels, slot, ticket), ctx_.raw());
+    }
+    // Whether the FLAC decoders on this batcher send a batch whose every word fits int16_t as int16_t: SYMACCEL_NARROW_INPUT=1 when the
+    // batcher is made, or set_narrow_input(true); otherwise every batch goes up wide, as it always did.  Read by a decoder when it attaches.
+    bool narrow_input() const { return narrow_input_; }
+    void set_narrow_input(bool on) { narrow_input_ = on; }
     // The process-wide batcher (the Rust shim's Pool::shared(), bindings/rust/symphonia-accel-hip/src/ctx.rs): device 0, the library's
     // default flush size, created on first use and never destroyed (decoders of any thread may hold it until the process ends).  This is
     // what a factory that sees (params, options) alone -- CodecRegistry::make_audio_decoder below, registry.rs:330-341 -- builds through.
@@ -173,6 +187,7 @@ public:
 private:
     Context &ctx_;
     symaccel_batcher *b_ = nullptr;
+    bool narrow_input_ = false;
 };
 
 namespace dsp {
@@ -605,6 +620,12 @@ struct FinalizeResult {  // codecs/audio.rs:230-236
 // registry's AudioDecoderOptions::verify), `published(i)` when packet i of the current batch is handed out, `rewind()` when whatever
 // was computed beyond the last packet handed out is dropped (a seek, skipped packets, an error), `set_replaying(bool)` around the
 // one-packet replay, which must not count, and `finalize_result()`.
+// ... and one whose plane 0 may go up as int16_t says so per batch, before the slot is reserved: `input_format(batch)` = 0 or
+// SYMACCEL_FMT_S16 (symaccel_batcher_reserve_io); its fill_slot() then writes plane 0 in that format.
+template <class C, class = void>
+struct has_input_format : std::false_type {};
+template <class C>
+struct has_input_format<C, std::void_t<decltype(&C::input_format)>> : std::true_type {};
 template <class C, class = void>
 struct has_finalize_result : std::false_type {};
 template <class C>
@@ -769,6 +790,15 @@ public:
     const DecodedBytes &last_decoded_bytes() const { return bytes_; }
     std::size_t lookahead() const { return lookahead_; }
     std::size_t batches_run() const { return batches_; }
+    // the batches this decoder submitted with plane 0 as int16_t / as int32_t (a codec with input_format(): Flac; 0 for the others)
+    std::size_t narrow_batches() const {
+        if constexpr (has_input_format<Codec>::value) return codec_.narrow_batches();
+        else return 0;
+    }
+    std::size_t wide_batches() const {
+        if constexpr (has_input_format<Codec>::value) return codec_.wide_batches();
+        else return 0;
+    }
 
 private:
     std::vector<Packet> gather(const Packet *first) {
@@ -811,7 +841,9 @@ private:
         if constexpr (Codec::kBatchKind != 0) {
             symaccel_batch_slot slot;
             if constexpr (has_prepare<Codec>::value) codec_.prepare(batch);
-            reserve(batch.size(), &slot, &next_ticket_);
+            int in_fmt = 0;
+            if constexpr (has_input_format<Codec>::value) in_fmt = codec_.input_format(batch);
+            reserve(batch.size(), &slot, &next_ticket_, in_fmt);
             next_live_ = true;
             try {
                 codec_.fill_slot(batch, slot);  // the parsed packets and the carried state go into the page-locked slot
@@ -827,9 +859,12 @@ private:
         }
     }
     // a slot for a batch of n packets: the native planes, or (set_output) the interleave groups of the caller's format
-    void reserve(std::size_t n, symaccel_batch_slot *sl, std::uint64_t *t) {
+    void reserve(std::size_t n, symaccel_batch_slot *sl, std::uint64_t *t, int in_fmt = 0) {
         if constexpr (Codec::kBatchKind != 0) {
-            if (out_fmt_ == SampleFormat::Native)
+            if (in_fmt != 0)  // (a codec with input_format(): plane 0 as int16_t, widened in the gather)
+                batcher_->reserve_io(Codec::kBatchKind, codec_.batch_param(), codec_.batch_chains(n), codec_.batch_units(n), in_fmt,
+                                     out_fmt_ == SampleFormat::Native ? 0 : static_cast<int>(out_fmt_), out_interleaved_ ? (int)codec_.channels() : 1, sl, t);
+            else if (out_fmt_ == SampleFormat::Native)
                 check(symaccel_batcher_reserve(batcher_->raw(), Codec::kBatchKind, codec_.batch_param(), codec_.batch_chains(n), codec_.batch_units(n), sl, t), ctx_.raw());
             else
                 check(symaccel_batcher_reserve_fmt(batcher_->raw(), Codec::kBatchKind, codec_.batch_param(), codec_.batch_chains(n), codec_.batch_units(n),
@@ -1783,7 +1818,21 @@ struct Flac {
     static constexpr int kBatchKind = SYMACCEL_BATCH_FLAC_RESTORE;
     static constexpr bool kDirect = false;
     struct BatchView {};
-    void attach(Batcher &) {}
+    void attach(Batcher &b) { narrow_ok_ = b.narrow_input(); }
+    // The input format of a batch (LookaheadDecoder asks before it reserves: the format belongs to the reservation): int16_t when EVERY
+    // warm-up sample and residual of the batch fits -- the 16-bit streams, but for a side channel's 17-bit warm-up here and there --, else
+    // the native words exactly as before.  Per batch; nothing else about the decoder depends on it.
+    int input_format(const std::vector<Packet> &batch) {
+        std::uint32_t miss = 0;
+        if (narrow_ok_)
+            for (const Packet &p : batch)
+                for (const std::int32_t v : p.words) miss |= (std::uint32_t)v ^ (std::uint32_t)(std::int32_t)(std::int16_t)v;
+        narrow_next_ = narrow_ok_ && miss == 0;
+        ++(narrow_next_ ? narrow_batches_ : wide_batches_);
+        return narrow_next_ ? SYMACCEL_FMT_S16 : 0;
+    }
+    std::size_t narrow_batches() const { return narrow_batches_; }
+    std::size_t wide_batches() const { return wide_batches_; }
     int batch_param() const {
         if (hashing()) return (nch_ == 2 ? (int)(0x300u | shift_) : 0x200) | (int)((nch_ - 1) << 12);
         return nch_ == 2 ? (int)(0x100u | shift_) : 0;
@@ -1803,9 +1852,15 @@ struct Flac {
                 throw std::invalid_argument("Flac: packet shape");
             next_lens_[i] = p.blocksize;
             for (std::size_t c = 0; c < nch_; ++c) {
-                std::int32_t *row = words + (i * nch_ + c) * max_bs_;
-                std::copy_n(p.words.data() + c * p.blocksize, p.blocksize, row);
-                std::fill(row + p.blocksize, row + max_bs_, 0);  // (restoring the padding is harmless: it is never published)
+                if (narrow_next_) {  // (input_format() found that every word fits: packed straight into the slot)
+                    std::int16_t *row = static_cast<std::int16_t *>(slot.input[0]) + (i * nch_ + c) * max_bs_;
+                    if (!symaccel_host_narrow_s16(p.words.data() + c * p.blocksize, row, p.blocksize)) throw std::logic_error("Flac: a narrow batch with a wide word");
+                    std::fill(row + p.blocksize, row + max_bs_, (std::int16_t)0);
+                } else {
+                    std::int32_t *row = words + (i * nch_ + c) * max_bs_;
+                    std::copy_n(p.words.data() + c * p.blocksize, p.blocksize, row);
+                    std::fill(row + p.blocksize, row + max_bs_, 0);  // (restoring the padding is harmless: it is never published)
+                }
                 desc[i * nch_ + c] = p.desc[c];
                 std::copy_n(p.coeffs.data() + c * 32, 32, coeffs + (i * nch_ + c) * 32);
             }
@@ -1898,6 +1953,8 @@ private:
     std::size_t max_bs_;
     std::optional<std::array<std::uint8_t, 16>> expected_;
     bool verify_ = false, replaying_ = false;
+    bool narrow_ok_ = false, narrow_next_ = false;  // the batcher's setting (attach); the format of the batch being submitted
+    std::size_t narrow_batches_ = 0, wide_batches_ = 0;
     symaccel_md5_state published_{}, chain_end_{};
     std::vector<symaccel_md5_state> cps_;  // the state after every packet of the current batch
     std::vector<symaccel_flac_md5_frame> frames_;

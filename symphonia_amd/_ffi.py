@@ -71,6 +71,7 @@ ABI_SYMBOLS = [
     "symaccel_flac_md5_finish_device", "symaccel_batcher_submit_flac_verify",
     "symaccel_sample_bytes", "symaccel_pcm_convert_device", "symaccel_pcm_convert",
     "symaccel_batcher_reserve_fmt", "symaccel_batcher_submit_fmt",
+    "symaccel_batcher_reserve_io", "symaccel_batcher_submit_io", "symaccel_host_narrow_s16",
     "symaccel_adpcm_block_bytes", "symaccel_adpcm_decode_device", "symaccel_adpcm_decode",
     "symaccel_batcher_submit_adpcm_decode",
     "symaccel_pcm_coded_bytes", "symaccel_pcm_native_bytes", "symaccel_pcm_decode_device", "symaccel_pcm_decode",
@@ -162,6 +163,9 @@ class Library:
         d.symaccel_batcher_submit.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _vp, _vp, C.POINTER(C.c_uint64)]
         d.symaccel_batcher_reserve_fmt.argtypes = [_vp, _i, _i, _sz, _sz, _i, _i, _vp, C.POINTER(C.c_uint64)]
         d.symaccel_batcher_submit_fmt.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _vp, _vp, _i, _i, C.POINTER(C.c_uint64)]
+        d.symaccel_batcher_reserve_io.argtypes = [_vp, _i, _i, _sz, _sz, _i, _i, _i, _vp, C.POINTER(C.c_uint64)]
+        d.symaccel_batcher_submit_io.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _vp, _vp, _i, _i, _i, C.POINTER(C.c_uint64)]
+        d.symaccel_host_narrow_s16.argtypes = [_vp, _vp, _sz]
         d.symaccel_batcher_collect.argtypes = [_vp, C.c_uint64]
         d.symaccel_batcher_abandon.argtypes = [_vp, C.c_uint64]
         d.symaccel_batcher_submit_aac_synth.argtypes = [_vp, _vp, _vp, _vp, _vp, _sz, _sz, C.POINTER(C.c_uint64)]

@@ -1105,11 +1105,12 @@ class Batcher:
     def _check(self, st):
         return self.ctx.lib.check(st, self.ctx.handle)
 
-    def submit(self, kind, param, inputs, states, out, out_format=0, channels=0, n_chains=None, units=None):
+    def submit(self, kind, param, inputs, states, out, out_format=0, channels=0, n_chains=None, units=None, in_fmt=0):
         """inputs / states / out: C-contiguous numpy arrays ([chain][unit]... / [chain]...); the states are updated and `out` is
         filled by collect().  out_format (a FMT_* value or name) / channels: symaccel_batcher_submit_fmt -- `out` then receives
         [n_chains / channels][samples][channels] samples of that format (a byte buffer of the native planes' size always holds it) and
-        n_chains / units are taken from inputs[0]'s shape unless given."""
+        n_chains / units are taken from inputs[0]'s shape unless given.  in_fmt "s16" (FLAC_RESTORE / ALAC_PREDICT): inputs[0] holds
+        int16 words, widened in the gather (symaccel_batcher_submit_io)."""
         shaped = out if not out_format else inputs[0]
         n_chains, units = int(shaped.shape[0] if n_chains is None else n_chains), int(shaped.shape[1] if units is None else units)
         ins = (C.c_void_p * 6)(*[a.ctypes.data if a is not None else None for a in list(inputs) + [None] * (6 - len(inputs))])
@@ -1117,7 +1118,10 @@ class Batcher:
         for a in list(inputs) + list(states) + [out]:
             assert a is None or a.flags["C_CONTIGUOUS"]
         t = C.c_uint64()
-        if out_format:
+        if in_fmt:
+            self._check(self.dll.symaccel_batcher_submit_io(self.handle, int(kind), int(param), n_chains, units, ins, sts, out.ctypes.data,
+                                                            sample_format(in_fmt), sample_format(out_format) if out_format else 0, int(channels), C.byref(t)))
+        elif out_format:
             self._check(self.dll.symaccel_batcher_submit_fmt(self.handle, int(kind), int(param), n_chains, units, ins, sts, out.ctypes.data,
                                                              sample_format(out_format), int(channels), C.byref(t)))
         else:
@@ -1249,11 +1253,15 @@ class Batcher:
                                                                 frames, pcm.ctypes.data, C.byref(t)))
         return int(t.value)
 
-    def reserve(self, kind, param, n_chains, units, out_format=0, channels=0):
+    def reserve(self, kind, param, n_chains, units, out_format=0, channels=0, in_fmt=0):
         """out_format / channels: symaccel_batcher_reserve_fmt -- slot.out then receives interleaved samples of that format, slot.out_bytes
-        of them valid (wait() returns the count the launch wrote)"""
+        of them valid (wait() returns the count the launch wrote).  in_fmt "s16" (FLAC_RESTORE / ALAC_PREDICT): slot.input[0] takes int16
+        words, slot.input_bytes[0] of them (symaccel_batcher_reserve_io)"""
         slot, t = BatchSlot(), C.c_uint64()
-        if out_format:
+        if in_fmt:
+            self._check(self.dll.symaccel_batcher_reserve_io(self.handle, int(kind), int(param), int(n_chains), int(units), sample_format(in_fmt),
+                                                             sample_format(out_format) if out_format else 0, int(channels), C.byref(slot), C.byref(t)))
+        elif out_format:
             self._check(self.dll.symaccel_batcher_reserve_fmt(self.handle, int(kind), int(param), int(n_chains), int(units), sample_format(out_format),
                                                               int(channels), C.byref(slot), C.byref(t)))
         else:

@@ -4,6 +4,9 @@
 // device's address space, so the kernel reads (gather) or writes (scatter) the slots directly; the descriptor list itself is read
 // from page-locked memory too.  A workgroup takes one piece of at most 16 KiB: four 16-byte loads per lane in flight, then the
 // stores -- with a grid of thousands of pieces the link sees enough outstanding reads to run at its rate.
+// Two launches do more than copy: the scatter of a chunk with tickets that want their PCM in a sample format converts and interleaves
+// (batch_scatter_convert_kernel), the gather of a chunk with tickets whose FLAC / ALAC words came as int16_t widens them
+// (batch_gather_widen_kernel); every other chunk is moved by batch_copy_kernel.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -180,6 +183,61 @@ __global__ __launch_bounds__(256) void batch_scatter_convert_kernel(const BatchC
     }
 }
 
+// The gather of a chunk that holds WIDENING pieces (BatchCopyDesc::pad & kBatchPieceWiden: batcher.cpp, tickets whose plane 0 came as
+// int16_t -- symaccel_batcher_reserve_io): the mirror image of the converting scatter.  `src` = int16_t words in the page-locked slot (a
+// row of odd length starts at a 2-byte boundary), `dst` = int32_t words in HBM, `bytes` = the DESTINATION's (<= kBatchCopyPiece: 4096
+// words, 8 KiB of source).  The source is cut at its 16-byte boundaries: up to 7 words of a ragged head, a body of 16-byte loads (8
+// words each: at most 512, two per lane), up to 7 words of a ragged tail; every load of a lane -- two of the body, one of the head or
+// the tail -- is issued before its first store.  A body load becomes two 16-byte stores where the destination behind the head is 16-byte
+// aligned, eight 4-byte stores where it is not.  Nothing outside [src, src + bytes / 2) is read, nothing outside [dst, dst + bytes) written.
+// (a compiler vector, not HIP's int4: an int4 built from components is stored word by word, this is ONE 16-byte store)
+typedef int widen_v4i __attribute__((vector_size(16)));
+__device__ __forceinline__ void widen_store(int32_t *out, const uint4 v, const bool aligned) {
+    const int w0 = (int)(v.x << 16) >> 16, w1 = (int)v.x >> 16, w2 = (int)(v.y << 16) >> 16, w3 = (int)v.y >> 16;
+    const int w4 = (int)(v.z << 16) >> 16, w5 = (int)v.z >> 16, w6 = (int)(v.w << 16) >> 16, w7 = (int)v.w >> 16;
+    if (aligned) {
+        widen_v4i *o = reinterpret_cast<widen_v4i *>(out);
+        o[0] = widen_v4i{w0, w1, w2, w3};
+        o[1] = widen_v4i{w4, w5, w6, w7};
+    } else {
+        out[0] = w0, out[1] = w1, out[2] = w2, out[3] = w3;
+        out[4] = w4, out[5] = w5, out[6] = w6, out[7] = w7;
+    }
+}
+
+__device__ __forceinline__ void batch_widen_piece(const BatchCopyDesc d, const unsigned tid) {
+    const int16_t *src = static_cast<const int16_t *>(d.src);
+    int32_t *dst = static_cast<int32_t *>(d.dst);
+    const unsigned n = d.bytes / 4u;  // words, <= 4096
+    const unsigned to_boundary = (unsigned)((0u - reinterpret_cast<uintptr_t>(src)) & 15u) / 2u;
+    const unsigned head = to_boundary < n ? to_boundary : n;
+    const unsigned nb = (n - head) / 8u, tail0 = head + 8u * nb;  // nb <= 512
+    const uint4 *body = reinterpret_cast<const uint4 *>(src + head);
+    int32_t *out = dst + head;
+    const bool aligned = (reinterpret_cast<uintptr_t>(out) & 15u) == 0;
+    const bool p0 = tid < nb, p1 = tid + 256u < nb;
+    // the ragged ends: lanes 0..7 take the head's words, lanes 8..15 the tail's
+    const unsigned r = tid < 8u ? tid : tail0 + (tid - 8u);
+    const bool pr = tid < 8u ? tid < head : (tid < 16u && r < n);
+    uint4 v0 = {}, v1 = {};
+    int16_t e = 0;
+    if (p0) v0 = body[tid];
+    if (p1) v1 = body[tid + 256u];
+    if (pr) e = src[r];
+    if (p0) widen_store(out + 8u * tid, v0, aligned);
+    if (p1) widen_store(out + 8u * (tid + 256u), v1, aligned);
+    if (pr) dst[r] = e;
+}
+
+// (plain pieces -- descriptors, coefficients, state, the rows of the tickets that came wide -- as batch_scatter_convert_kernel copies its own)
+__global__ __launch_bounds__(256) void batch_gather_widen_kernel(const BatchCopyDesc *__restrict__ descs, unsigned n_pieces) {
+    for (unsigned piece = blockIdx.x; piece < n_pieces; piece += gridDim.x) {
+        const BatchCopyDesc d = descs[piece];
+        if (d.pad & kBatchPieceWiden) batch_widen_piece(d, threadIdx.x);
+        else batch_copy_piece_beside_tiles(d, threadIdx.x);
+    }
+}
+
 }  // namespace
 
 // (the caller has checked formats, channel count, alignment and sizes: symaccel_pcm_convert_device)
@@ -223,7 +281,7 @@ int launch_batch_flag(symaccel_ctx *ctx, hipStream_t stream, uint64_t *h_flag, u
     return SYMACCEL_OK;
 }
 
-int launch_batch_copy(symaccel_ctx *ctx, hipStream_t stream, const BatchCopyDesc *descs, size_t n, bool scatter, size_t pcm_plane_stride) {
+int launch_batch_copy(symaccel_ctx *ctx, hipStream_t stream, const BatchCopyDesc *descs, size_t n, bool scatter, size_t pcm_plane_stride, bool widening) {
     if (n == 0) return SYMACCEL_OK;
     if (n > 0x7fffffffu) return SYMACCEL_ERR_INVALID_ARG;
     // workgroups per copy launch.  64: the link needs few -- a copy kernel that fills the device keeps the synthesis kernel and the copy of
@@ -240,7 +298,9 @@ int launch_batch_copy(symaccel_ctx *ctx, hipStream_t stream, const BatchCopyDesc
         return e && std::atoi(e) != 0;
     }();
     // (pcm_plane_stride != 0: the list holds converting pieces -- only then; every other launch is the plain kernel, as before)
+    // (widening: the list of a gather holds widening pieces -- likewise)
     if (pcm_plane_stride) hipLaunchKernelGGL(batch_scatter_convert_kernel, dim3(grid), dim3(256), 0, stream, descs, (unsigned)n, pcm_plane_stride);
+    else if (widening && !scatter) hipLaunchKernelGGL(batch_gather_widen_kernel, dim3(grid), dim3(256), 0, stream, descs, (unsigned)n);
     else if (nt && scatter) hipLaunchKernelGGL((batch_copy_kernel<true, 1>), dim3(grid), dim3(256), 0, stream, descs, (unsigned)n);
     else if (nt) hipLaunchKernelGGL((batch_copy_kernel<true, 0>), dim3(grid), dim3(256), 0, stream, descs, (unsigned)n);
     else if (scatter) hipLaunchKernelGGL((batch_copy_kernel<false, 1>), dim3(grid), dim3(256), 0, stream, descs, (unsigned)n);

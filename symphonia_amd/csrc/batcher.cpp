@@ -249,6 +249,9 @@ struct Ticket {
     int out_fmt = 0;
     uint32_t channels = 0;
     size_t out_valid = 0;
+    // the input format (symaccel_batcher_reserve_io): 0 = the native planes, SYMACCEL_FMT_S16 = plane 0 of the slot holds int16_t words
+    // -- the first half of the region the native plane (and the result, in place) has
+    int in_fmt = 0;
 };
 
 enum class GroupState { Free, Open, Closed, Launching, Launched };
@@ -698,15 +701,26 @@ void gather_rows(const Group *g, const TicketView &t, Pieces &pw) {
     for (size_t c = 0; c < t.n_chains; ++c) pw.bulk(t.slot + t.lay.in[0] + c * g->ps.in[0], g->d_in[0] + ((size_t)t.first_chain + c) * g->row_pitch, g->ps.in[0]);
 }
 
-// gather: the submissions' planes into the chain-major device arrays, and the chunk's lists
-void build_gather(Group *g, const Chunk &ch, Pieces &pw) {
+// FLAC / ALAC, a submission whose plane 0 came as int16_t (symaccel_batcher_reserve_io): widening pieces, row by row where the device
+// plane is padded, the whole plane in one run where its rows are back to back
+void gather_narrow(const Group *g, const TicketView &t, Pieces &pw) {
+    const size_t row = g->ps.in[0];  // (the destination's bytes; the slot's rows are half of it)
+    const char *src = t.slot + t.lay.in[0];
+    if (!g->row_pitch) return pw.widen(src, g->d_in[0] + (size_t)t.first_chain * row, row * t.n_chains);
+    for (size_t c = 0; c < t.n_chains; ++c) pw.widen(src + c * (row / 2), g->d_in[0] + ((size_t)t.first_chain + c) * g->row_pitch, row);
+}
+
+// gather: the submissions' planes into the chain-major device arrays, and the chunk's lists; true if the list holds widening pieces
+bool build_gather(Group *g, const Chunk &ch, Pieces &pw) {
+    bool widening = false;
     const PlaneSizes &ps = g->ps;
     const bool verify = g->kind == SYMACCEL_BATCH_FLAC_RESTORE && flac_verify_param(g->param).verify;
     for (size_t ti = ch.t0; ti < ch.t0 + ch.nt; ++ti) {
         const TicketView &t = g->views[ti];
         for (int i = 0; i < ps.n_in; ++i) {
             if (ps.in_host_only[i]) continue;
-            if (i == 0 && vorbis_kind(g->kind)) gather_vorbis_spectra(g, t, pw);
+            if (i == 0 && t.in_fmt) gather_narrow(g, t, pw), widening = true;
+            else if (i == 0 && vorbis_kind(g->kind)) gather_vorbis_spectra(g, t, pw);
             else if (i == 0 && g->row_pitch) gather_rows(g, t, pw);
             else pw.bulk(t.slot + t.lay.in[i], g->d_in[i] + (ps.in_per_ticket[i] ? ti : (size_t)t.first_chain / ps.in_div[i]) * ps.in[i], t.lay.in_bytes[i]);
         }
@@ -718,6 +732,7 @@ void build_gather(Group *g, const Chunk &ch, Pieces &pw) {
     if (g->kind == SYMACCEL_BATCH_MP3_DECODE) g->mp3.build(g->views, ch, pw);
     if (g->kind == SYMACCEL_BATCH_AAC_DECODE) g->aac.build(g->views, ch, g->units, pw);
     if (g->kind == SYMACCEL_BATCH_VORBIS_DECODE) g->vb.build(g->views, ch, vorbis_param(g->param, g->units), g->units, pw);
+    return widening;
 }
 
 // The verify forms of FLAC_RESTORE: the unfused restore at the group's row pitch, then ONE MD5 launch over the chunk's submissions, a
@@ -816,14 +831,14 @@ void build_scatter(const Group *g, const Chunk &ch, Pieces &pw, size_t *pcm_stri
 }
 
 // the pieces [first, pw.w) as ONE copy launch on `s`, the bulk planes that go through a copy engine in front of it
-int enqueue_copies(symaccel_ctx *ctx, hipStream_t s, Pieces &pw, const BatchCopyDesc *first, bool scatter, size_t pcm_stride) {
+int enqueue_copies(symaccel_ctx *ctx, hipStream_t s, Pieces &pw, const BatchCopyDesc *first, bool scatter, size_t pcm_stride, bool widening = false) {
     if (pw.overflow) {  // (cannot happen while piece_bound() counts every contributor; nothing was written beyond the area)
         ctx->last_error = "batcher: a launch needs more copy pieces than piece_bound() counted";
         return SYMACCEL_ERR_DEVICE;
     }
     for (const Pieces::Dma &m : pw.dma) SYM_GPU(ctx, hipMemcpyAsync(m.dst, m.src, m.bytes, scatter ? hipMemcpyDeviceToHost : hipMemcpyHostToDevice, s));
     pw.dma.clear();
-    return launch_batch_copy(ctx, s, first, (size_t)(pw.w - first), scatter, pcm_stride);
+    return launch_batch_copy(ctx, s, first, (size_t)(pw.w - first), scatter, pcm_stride, widening);
 }
 
 // Everything of a closed group: per chunk of submissions ONE gather launch (slots -> HBM, the kernels' chain-major layout), the
@@ -844,9 +859,9 @@ int launch_group_inner(Lane *lane, Group *g, uint64_t *n_chunks, uint64_t *api_n
         const Chunk ch = next_chunk(g, t0);
         const int e = (int)(k & 1);
         const BatchCopyDesc *g0 = pw.w;
-        build_gather(g, ch, pw);
+        const bool widening = build_gather(g, ch, pw);
         const Clock::time_point api0 = Clock::now();
-        SYM_TRY(enqueue_copies(ctx, ctx->stage_in, pw, g0, false, 0));
+        SYM_TRY(enqueue_copies(ctx, ctx->stage_in, pw, g0, false, 0, widening));
         SYM_GPU(ctx, hipEventRecord(blk->ev_in[e], ctx->stage_in));
         SYM_GPU(ctx, hipStreamWaitEvent(ctx->stream, blk->ev_in[e], 0));
         SYM_TRY(launch_chunk(ctx, g, ch));
@@ -948,6 +963,7 @@ void flush_group(symaccel_batcher *b, Group *g, std::unique_lock<std::mutex> &lo
         for (size_t i = 0; i < g->tickets; ++i) {
             const Ticket &t = b->tickets[g->ticket_ids[i]];
             g->views[i] = TicketView{t.slot, t.first_chain, t.n_chains, SYMACCEL_OK, t.out_fmt, t.channels};
+            g->views[i].in_fmt = t.in_fmt;
             if (t.committed_at != Clock::time_point{}) b->stats.commit_to_launch_ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(closing - t.committed_at).count();
         }
         if (g->kind == SYMACCEL_BATCH_AAC_DECODE && g->param >= 0) g->aac.maps = b->bands[(size_t)g->param].maps;  // (the index was checked by reserve())
@@ -1064,6 +1080,7 @@ void fill_slot(const Group *g, const Ticket *t, symaccel_batch_slot *slot) {
         slot->input[i] = t->slot + l.in[i];
         slot->input_bytes[i] = l.in_bytes[i];
     }
+    if (t->in_fmt) slot->input_bytes[0] = l.in_bytes[0] / 2;  // (int16_t words: the front half of the native plane's region)
     for (int i = 0; i < g->ps.n_state; ++i) {
         slot->state[i] = t->slot + l.state[i];
         slot->state_bytes[i] = l.state_bytes[i];
@@ -1178,6 +1195,13 @@ int symaccel_batcher_reserve(symaccel_batcher *b, int kind, int param, size_t n_
 
 int symaccel_batcher_reserve_fmt(symaccel_batcher *b, int kind, int param, size_t n_chains, size_t units_per_chain, int out_fmt, int channels,
                                  symaccel_batch_slot *slot, uint64_t *ticket) {
+    return symaccel_batcher_reserve_io(b, kind, param, n_chains, units_per_chain, 0, out_fmt, channels, slot, ticket);
+}
+
+int symaccel_batcher_reserve_io(symaccel_batcher *b, int kind, int param, size_t n_chains, size_t units_per_chain, int in_fmt, int out_fmt,
+                                int channels, symaccel_batch_slot *slot, uint64_t *ticket) {
+    // (the widening happens in the gather, before any kernel of the kind sees the plane: every param form of the two kinds takes it)
+    if (in_fmt != 0 && (in_fmt != SYMACCEL_FMT_S16 || !serial_kind(kind))) return SYMACCEL_ERR_INVALID_ARG;
     if (!b || !slot || !ticket || n_chains == 0 || n_chains > 0x7fffffffu) return SYMACCEL_ERR_INVALID_ARG;
     // (a PCM packet of 0 frames is a packet like any other -- lib.rs:320: floor(len / frame bytes) -- with empty planes: it takes a ticket,
     // rides in the group of its shape and comes back with 0 bytes)
@@ -1240,6 +1264,7 @@ int symaccel_batcher_reserve_fmt(symaccel_batcher *b, int kind, int param, size_
         t->channels = (uint32_t)channels;
         t->out_valid = lay.out_bytes / 4 * symaccel_sample_bytes(out_fmt);
     }
+    t->in_fmt = in_fmt;
     g->ticket_ids.push_back(idx);
     g->chains += n_chains;
     g->tickets += 1;
@@ -1398,6 +1423,11 @@ int symaccel_batcher_submit(symaccel_batcher *b, int kind, int param, size_t n_c
 
 int symaccel_batcher_submit_fmt(symaccel_batcher *b, int kind, int param, size_t n_chains, size_t units_per_chain, const void **in,
                                 void **state_io, void *out, int out_fmt, int channels, uint64_t *ticket) {
+    return symaccel_batcher_submit_io(b, kind, param, n_chains, units_per_chain, in, state_io, out, 0, out_fmt, channels, ticket);
+}
+
+int symaccel_batcher_submit_io(symaccel_batcher *b, int kind, int param, size_t n_chains, size_t units_per_chain, const void **in,
+                               void **state_io, void *out, int in_fmt, int out_fmt, int channels, uint64_t *ticket) {
     if (!b || !in || !state_io || !out || !ticket) return SYMACCEL_ERR_INVALID_ARG;
     if (kind == SYMACCEL_BATCH_AAC_DECODE) return SYMACCEL_ERR_INVALID_ARG;  // (symaccel_batcher_submit_aac_decode writes the blob)
     PlaneSizes ps;
@@ -1410,7 +1440,7 @@ int symaccel_batcher_submit_fmt(symaccel_batcher *b, int kind, int param, size_t
         if (!state_io[i]) return SYMACCEL_ERR_INVALID_ARG;
     symaccel_batch_slot slot;
     uint64_t id = 0;
-    SYM_TRY(symaccel_batcher_reserve_fmt(b, kind, param, n_chains, units_per_chain, out_fmt, channels, &slot, &id));
+    SYM_TRY(symaccel_batcher_reserve_io(b, kind, param, n_chains, units_per_chain, in_fmt, out_fmt, channels, &slot, &id));
     for (int i = 0; i < ps.n_in; ++i) {
         if (in[i])
             std::memcpy(slot.input[i], in[i], slot.input_bytes[i]);
@@ -1620,6 +1650,18 @@ int symaccel_batcher_submit_alac_predict(symaccel_batcher *b, int32_t *buf_io, c
     const void *in[kMaxIn] = {buf_io, desc, coeffs, pair_weight, pair_shift, nullptr};
     void *st[3] = {nullptr, nullptr, nullptr};
     return symaccel_batcher_submit(b, SYMACCEL_BATCH_ALAC_PREDICT, pair_weight ? 0x100 : 0, n_blocks, blocksize, in, st, buf_io, ticket);
+}
+
+int symaccel_host_narrow_s16(const int32_t *src, int16_t *dst, size_t n) {
+    if (n && (!src || !dst)) return 0;
+    // one pass: every word is written as it is read, and what did not fit is OR-ed up -- no branch in the loop, so it vectorises
+    uint32_t miss = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const int32_t v = src[i];
+        dst[i] = (int16_t)v;
+        miss |= (uint32_t)v ^ (uint32_t)(int32_t)(int16_t)v;
+    }
+    return miss == 0;
 }
 
 int symaccel_batcher_collect(symaccel_batcher *b, uint64_t ticket) {

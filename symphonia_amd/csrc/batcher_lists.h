@@ -97,6 +97,7 @@ struct TicketView {
     int out_fmt = 0;
     uint32_t channels = 0;
     size_t out_valid = 0;
+    int in_fmt = 0;                // 0, or SYMACCEL_FMT_S16: plane 0 of the slot holds int16_t words (FLAC_RESTORE / ALAC_PREDICT, symaccel_batcher_reserve_io)
     int fmt_status = SYMACCEL_OK;  // what the output format has to say about the submission (Vorbis: an interleave group whose chains disagree)
     SlotLayout lay;
     const VorbisUsed *used = nullptr;  // the two Vorbis kinds: what the blocks of chain c fill, used[c]
@@ -149,6 +150,11 @@ struct Pieces {
     void add(const void *src, void *dst, size_t bytes) {
         for (size_t o = 0; o < bytes; o += kBatchCopyPiece)
             piece(static_cast<const char *>(src) + o, static_cast<char *>(dst) + o, std::min(kBatchCopyPiece, bytes - o), 0);
+    }
+    // int16_t words of a slot -> int32_t words of the device plane: cut by the DESTINATION's bytes, so that a narrow plane is as many
+    // pieces as the same plane sent wide (piece_bound() counts it as that); never through a copy engine, which cannot widen
+    void widen(const char *src, char *dst, size_t dst_bytes) {
+        for (size_t o = 0; o < dst_bytes; o += kBatchCopyPiece) piece(src + o / 2, dst + o, std::min(kBatchCopyPiece, dst_bytes - o), kBatchPieceWiden);
     }
     void bulk(const char *src, char *dst, size_t bytes) {
         if (dma_bytes && bytes >= dma_bytes) dma.push_back({src, dst, bytes});

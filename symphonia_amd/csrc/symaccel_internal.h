@@ -325,10 +325,15 @@ struct BatchCopyDesc {
 };
 constexpr size_t kBatchCopyPiece = 16384;
 constexpr uint32_t kBatchPieceConvert = 0x80000000u, kBatchPieceFromI32 = 0x10u;
+// A WIDENING piece of a gather (a ticket whose plane 0 came as int16_t, symaccel_batcher_reserve_io): src = int16_t words in the slot, dst =
+// int32_t words on the device, bytes = the destination's.  A bit the converting pieces' encoding leaves alone; launch_batch_copy's `widening`
+// says that a gather's list holds such pieces.
+constexpr uint32_t kBatchPieceWiden = 0x40000000u;
 constexpr uint32_t batch_piece_convert(bool from_i32, size_t frames, uint32_t channels, int dst_fmt) {  // the `pad` word of a converting piece
     return kBatchPieceConvert | (from_i32 ? kBatchPieceFromI32 : 0u) | ((uint32_t)frames << 12) | (channels << 8) | (uint32_t)dst_fmt;
 }
-int launch_batch_copy(symaccel_ctx *ctx, hipStream_t stream, const BatchCopyDesc *descs, size_t n, bool scatter, size_t pcm_plane_stride = 0);
+int launch_batch_copy(symaccel_ctx *ctx, hipStream_t stream, const BatchCopyDesc *descs, size_t n, bool scatter, size_t pcm_plane_stride = 0,
+                      bool widening = false);
 int launch_batch_flag(symaccel_ctx *ctx, hipStream_t stream, uint64_t *h_flag, uint64_t seq);  // (h_flag: page-locked host memory)
 // pcm_convert.h works in tiles: a frame range of one interleave group whose output is contiguous and at most kPcmTileBytes long (the piece
 // size of the batcher's scatter).  Frames of a tile: a multiple of 16 (so every tile of a group starts at the group's alignment modulo 16

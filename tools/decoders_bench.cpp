@@ -9,7 +9,7 @@
 // peek that copies the next packet out of a small pool (a parser writes its output somewhere too).  Nothing here links the
 // oracle: bench.py times the CPU port beside this with its own harness.  One JSON line on stdout.
 //
-//   decoders_bench --codec aac|aacd|mp3|mp3h|vorbis|flac --streams S --lookahead L --packets P --threads T [--per-stream] [--direct] [--in-phase] [--flush-mb M] [--lanes N] [--via-registry] [--out-format f32|s16|s24|u8|f32i] [--verify]
+//   decoders_bench --codec aac|aacd|mp3|mp3h|vorbis|flac --streams S --lookahead L --packets P --threads T [--per-stream] [--direct] [--in-phase] [--flush-mb M] [--lanes N] [--via-registry] [--out-format f32|s16|s24|u8|f32i] [--verify] [--bits 16|24] [--narrow 0|1]
 #include <array>
 #include <atomic>
 #include <chrono>
@@ -43,6 +43,11 @@ struct Args {
     // path without a conversion; s16 / s24 / u8 / f32i = interleaved samples of that format, converted in the batcher's scatter
     // (LookaheadDecoder::set_output; f32i: f32, interleaved)
     std::string out_format = "f32";
+    // --bits 16 (FLAC): a pool of 16-bit packets whose every warm-up sample and residual fits int16_t -- what the decoders send up as
+    // int16_t (symaccel_batcher_reserve_io).  --narrow 0|1 forces that choice (Batcher::set_narrow_input); without it the batcher's own
+    // setting holds (SYMACCEL_NARROW_INPUT).  --narrow 0 is the transport every batch had before there was an input format.
+    size_t bits = 24;
+    int narrow = -1;
     SampleFormat format() const {
         if (out_format == "f32") return SampleFormat::Native;
         if (out_format == "s16") return SampleFormat::S16;
@@ -54,6 +59,7 @@ struct Args {
 };
 
 constexpr size_t kPool = 32;
+size_t g_flac_bits = 24;  // --bits: what make_pool<Flac> and params<Flac> build
 
 template <class Codec>
 std::vector<typename Codec::Packet> make_pool(unsigned seed);
@@ -126,6 +132,21 @@ template <>
 std::vector<Flac::Packet> make_pool<Flac>(unsigned seed) {  // BASELINE config 5's shape per packet: two subframes of 4096 samples, LPC order 32, 24 bits
     std::mt19937 rng(seed);
     std::vector<Flac::Packet> pool(kPool);
+    if (g_flac_bits == 16) {
+        // 16-bit: the same shape (LPC order 32, shift 12), every word inside int16_t.  Warm-ups within +-12000, residuals below 2^12, and
+        // coefficients within +-60: sum |c| / 2^12 < 0.47, so |s[n]| <= 4095 + 0.47 * max |s| stays at or below 12000 -- the restored samples,
+        // and their sums and differences in the decorrelation, stay inside 16 bits.
+        for (auto &p : pool) {
+            p.blocksize = 4096;
+            p.words.resize(2 * 4096);
+            for (size_t i = 0; i < p.words.size(); ++i) p.words[i] = i % 4096 < 32 ? (int32_t)(rng() % 24001) - 12000 : (int32_t)(rng() % 8191) - 4095;
+            p.desc.assign(2, symaccel_flac_desc{SYMACCEL_FLAC_LPC, 32, 12, 0});
+            p.coeffs.resize(2 * 32);
+            for (auto &c : p.coeffs) c = (int32_t)(rng() % 121) - 60;
+            p.pair_mode = (uint8_t)(rng() % 4);
+        }
+        return pool;
+    }
     for (auto &p : pool) {
         p.blocksize = 4096;
         p.words.resize(2 * 4096);
@@ -228,7 +249,7 @@ Mp3Huffman::Params params<Mp3Huffman>() { return Mp3Huffman::Params{2, 2, 0}; }
 template <>
 Vorbis::Params params<Vorbis>() { return Vorbis::Params{8, 8, 11}; }
 template <>
-Flac::Params params<Flac>() { return Flac::Params{2, 24, 4096}; }
+Flac::Params params<Flac>() { return Flac::Params{2, (std::uint32_t)g_flac_bits, 4096}; }
 
 // --verify: the digest a FLAC stream of `count[s]` packets pool[(i + salt[s]) % kPool], i = 0 .. count[s], must have.  The bytes validate.rs
 // hashes are the low three bytes of every decorrelated 24-bit sample, which are the upper three of the left-justified sample the decoder
@@ -272,6 +293,7 @@ std::vector<Digest> true_digests(Decoder &plain, const std::vector<Flac::Packet>
 
 template <class Codec>
 int run(const Args &a, const char *codec_name, size_t frames_per_packet, size_t bytes_in_per_packet) {
+    if (a.bits != 24 && !std::is_same<Codec, Flac>::value) throw std::invalid_argument("--bits: the FLAC pool");
     using Packet = typename Codec::Packet;
     using Decoder = LookaheadDecoder<Codec>;
     // --via-registry: the decoders come from CodecRegistry::make_audio_decoder, which is handed (params, options) and the packet source
@@ -295,6 +317,7 @@ int run(const Args &a, const char *codec_name, size_t frames_per_packet, size_t 
     }
     Context &ctx = a.via_registry ? batcher->context() : *own_ctx;
     if (batcher && a.lanes) check(symaccel_batcher_configure(batcher->raw(), (int)a.lanes, 0), ctx.raw());
+    if (batcher && a.narrow >= 0) batcher->set_narrow_input(a.narrow != 0);  // (before any decoder attaches)
     const std::vector<Packet> pool = make_pool<Codec>(17);
     struct Stream {
         size_t cursor = 0, limit = 0, salt = 0, pos = 0, lead = 0;
@@ -310,6 +333,7 @@ int run(const Args &a, const char *codec_name, size_t frames_per_packet, size_t 
     if (a.verify) {
         if constexpr (std::is_same<Codec, Flac>::value) {
             if (a.format() != SampleFormat::Native) throw std::invalid_argument("--verify: the planes are hashed as they are decoded (no --out-format)");
+            if (a.bits != 24) throw std::invalid_argument("--verify: the host-side digests are those of 24-bit samples (no --bits 16)");
             std::vector<size_t> salt(a.streams), count(a.streams);
             for (size_t s = 0; s < a.streams; ++s) salt[s] = s * 7, count[s] = total + lead_of(s);  // (what the two phases below decode of stream s)
             std::vector<Digest> want;
@@ -421,8 +445,11 @@ int run(const Args &a, const char *codec_name, size_t frames_per_packet, size_t 
     const double secs = std::chrono::duration<double>(Clock::now() - t0).count();
     symaccel_batcher_stats s1{};
     if (batcher) s1 = batcher->stats();
-    size_t batches = 0, verified = 0;
+    size_t batches = 0, verified = 0, narrow_batches = 0, wide_batches = 0;
     for (auto &st : streams) batches += st->dec->batches_run();
+    for (auto &st : streams) narrow_batches += st->dec->narrow_batches(), wide_batches += st->dec->wide_batches();
+    // (what went up per packet: half of the words' bytes if every batch went narrow; the counts cover the warm-up too)
+    if (narrow_batches && !wide_batches) bytes_in_per_packet -= frames_per_packet * params<Codec>().channels * 2;
     for (auto &st : streams) verified += st->dec->finalize().verify_ok.value_or(false) ? 1 : 0;
     if (a.verify && verified != a.streams) {
         std::fprintf(stderr, "--verify: %zu of %zu streams have their digest\n", verified, a.streams);
@@ -434,7 +461,7 @@ int run(const Args &a, const char *codec_name, size_t frames_per_packet, size_t 
                 "\"packets_per_s\": %.1f, \"frames_per_packet\": %zu, \"host_bytes_in_per_packet\": %zu, \"host_bytes_out_per_packet\": %zu, "
                 "\"GBps_each_way\": [%.3f, %.3f], \"decoder_batches\": %zu, \"launches\": %llu, \"kernel_launches\": %llu, \"max_chains_per_launch\": %llu, "
                 "\"staging_bytes\": %llu, \"staging_grew_bytes\": %llu, \"slots_peak\": [%llu, %llu], \"lanes\": %llu, \"mutex_wait_ms\": %.3f, \"mutex_contended\": %llu, \"launch_host_ms\": %.3f, \"launch_api_ms\": %.3f, \"lane_wait_ms\": %.3f, \"group_allocs\": %llu, \"blocks\": %llu, \"flag_wait_ms\": %.3f, \"commit_to_launch_ms_per_submission\": %.3f, \"waits\": %llu, \"waits_blocked\": %llu, \"launch_to_done_ms\": %.3f, "
-                "\"failed_tickets\": %llu, \"failures\": %zu, \"checksum\": %llu, \"out_format\": \"%s\", \"flag_wait_ns\": %llu, \"verify\": %s, \"streams_verified\": %zu}\n",
+                "\"failed_tickets\": %llu, \"failures\": %zu, \"checksum\": %llu, \"out_format\": \"%s\", \"flag_wait_ns\": %llu, \"verify\": %s, \"streams_verified\": %zu, \"bits\": %zu, \"narrow_batches\": %zu, \"wide_batches\": %zu}\n",
                 codec_name, a.via_registry ? "registry" : (batcher ? "batcher" : "per-stream"), a.direct ? "true" : "false", a.in_phase ? "true" : "false", a.streams, a.lookahead, std::min(a.threads, a.streams), n, secs, n / secs, frames_per_packet,
                 bytes_in_per_packet, frames_per_packet * params<Codec>().channels * out_sample_bytes, n * bytes_in_per_packet / secs / 1e9,
                 n * frames_per_packet * params<Codec>().channels * out_sample_bytes / secs / 1e9, batches,
@@ -444,7 +471,7 @@ int run(const Args &a, const char *codec_name, size_t frames_per_packet, size_t 
                 (double)(s1.launch_host_ns - s0.launch_host_ns) / 1e6, (double)(s1.launch_api_ns - s0.launch_api_ns) / 1e6,
                 (double)(s1.lane_wait_ns - s0.lane_wait_ns) / 1e6, (unsigned long long)(s1.group_allocs - s0.group_allocs), (unsigned long long)s1.blocks, (double)(s1.flag_wait_ns - s0.flag_wait_ns) / 1e6, (double)(s1.commit_to_launch_ns - s0.commit_to_launch_ns) / 1e6 / (double)std::max<uint64_t>(1, s1.submissions - s0.submissions), (unsigned long long)(s1.waits - s0.waits), (unsigned long long)(s1.waits_blocked - s0.waits_blocked), (double)(s1.launch_to_done_ns - s0.launch_to_done_ns) / 1e6 / (double)std::max<uint64_t>(1, s1.launches_timed - s0.launches_timed),
                 (unsigned long long)(s1.failed_tickets - s0.failed_tickets), failures.load(),
-                (unsigned long long)checksum.load(), a.out_format.c_str(), (unsigned long long)(s1.flag_wait_ns - s0.flag_wait_ns), a.verify ? "true" : "false", verified);
+                (unsigned long long)checksum.load(), a.out_format.c_str(), (unsigned long long)(s1.flag_wait_ns - s0.flag_wait_ns), a.verify ? "true" : "false", verified, a.bits, narrow_batches, wide_batches);
     return failures.load() ? 1 : 0;
 }
 
@@ -469,12 +496,15 @@ int main(int argc, char **argv) {
         else if (k == "--via-registry") a.via_registry = true;
         else if (k == "--verify") a.verify = true;
         else if (k == "--out-format" && i + 1 < argc) a.out_format = argv[++i];
+        else if (k == "--bits") a.bits = val();
+        else if (k == "--narrow") a.narrow = (int)val();
         else {
             std::fprintf(stderr, "unknown argument %s\n", k.c_str());
             return 2;
         }
     }
-    if (!a.streams || !a.lookahead || !a.packets || !a.threads) return 2;
+    if (!a.streams || !a.lookahead || !a.packets || !a.threads || (a.bits != 16 && a.bits != 24)) return 2;
+    g_flac_bits = a.bits;
     if (!a.warm) a.warm = 4 * a.lookahead;  // past the cold start (every stream's first batch is a launch of its own) and the pool's growth
     try {
         if (a.codec == "aac") return run<AacLc>(a, "aac", 1024, 2 * 1024 * 4 + 2);

@@ -129,6 +129,9 @@ def path_builtin(it, segs):
                 v = I.Enum(v.enum, v.variant, dict(v.f) if v.f else None)
             return Cell('Mutex', v)
         return I.Builtin(mutex_new, 'Mutex::new')
+    if head == 'env' and name == 'var':  # std::env::var: the interpreter's own environment
+        import os
+        return I.Builtin(lambda k: I.ok(os.environ[I.deref(k)]) if I.deref(k) in os.environ else I.err(I.Struct('VarError', {})), 'env::var')
     if head == 'OnceLock' and name == 'new':  # std::sync::OnceLock: an empty slot; get_or_init fills it once
         return I.Builtin(lambda: Cell('OnceLock', None), 'OnceLock::new')
     if head == 'HashMap' and name in ('new', 'with_capacity', 'default'):
