@@ -590,63 +590,87 @@ struct DecodedBytes {
     std::size_t plane_stride = 0;  // bytes between the channels of a planar result; 0 = interleaved
 };
 
-// A codec whose batcher kind delivers a format as [block][frame][channel] (ADPCM: the interleave group is one block's channels, the blocks
-// of a packet follow one another) says so with `kBlockInterleave`: publish() then finds a packet's bytes at its first block
-template <class C, class = void>
-struct has_block_interleave : std::false_type {};
-template <class C>
-struct has_block_interleave<C, std::void_t<decltype(C::kBlockInterleave)>> : std::true_type {};
-
-// A codec with no host parse stage (ADPCM) finds a packet's own errors -- a rejected preamble, a packet shorter than its blocks -- when the
-// batch is assembled.  It keeps them per packet (`packet_error(i)`), the packet runs as silence, and decode() throws the error when THAT
-// packet's turn comes: a packet fails alone (codecs/audio.rs:273-278), its neighbours in the look-ahead batch keep their PCM.
-template <class C, class = void>
-struct has_packet_errors : std::false_type {};
-template <class C>
-struct has_packet_errors<C, std::void_t<decltype(std::declval<const C &>().packet_error(std::size_t{}))>> : std::true_type {};
-
-// A codec whose slot shape depends on the packets of the batch (PCM: the frames of its longest packet) is shown the batch before the slot
-// is reserved: `prepare(batch)`.
-template <class C, class = void>
-struct has_prepare : std::false_type {};
-template <class C>
-struct has_prepare<C, std::void_t<decltype(&C::prepare)>> : std::true_type {};
-
 struct FinalizeResult {  // codecs/audio.rs:230-236
     std::optional<bool> verify_ok;
 };
 
-// A codec that verifies its stream (FLAC: the STREAMINFO MD5) is told about the decoder's life below it: `set_verify(bool)` (the
-// registry's AudioDecoderOptions::verify), `published(i)` when packet i of the current batch is handed out, `rewind()` when whatever
-// was computed beyond the last packet handed out is dropped (a seek, skipped packets, an error), `set_replaying(bool)` around the
-// one-packet replay, which must not count, and `finalize_result()`.
-// ... and one whose plane 0 may go up as int16_t says so per batch, before the slot is reserved: `input_format(batch)` = 0 or
-// SYMACCEL_FMT_S16 (symaccel_batcher_reserve_io); its fill_slot() then writes plane 0 in that format.
-template <class C, class = void>
-struct has_input_format : std::false_type {};
-template <class C>
-struct has_input_format<C, std::void_t<decltype(&C::input_format)>> : std::true_type {};
-template <class C, class = void>
-struct has_finalize_result : std::false_type {};
-template <class C>
-struct has_finalize_result<C, std::void_t<decltype(&C::finalize_result)>> : std::true_type {};
-template <class C, class = void>
-struct has_set_verify : std::false_type {};
-template <class C>
-struct has_set_verify<C, std::void_t<decltype(&C::set_verify)>> : std::true_type {};
-// (every hook is detected on its own: a codec supplies the ones it needs)
-template <class C, class = void>
-struct has_published : std::false_type {};
-template <class C>
-struct has_published<C, std::void_t<decltype(&C::published)>> : std::true_type {};
-template <class C, class = void>
-struct has_rewind : std::false_type {};
-template <class C>
-struct has_rewind<C, std::void_t<decltype(&C::rewind)>> : std::true_type {};
-template <class C, class = void>
-struct has_set_replaying : std::false_type {};
-template <class C>
-struct has_set_replaying<C, std::void_t<decltype(&C::set_replaying)>> : std::true_type {};
+// What LookaheadDecoder asks of a `Codec`.  Every codec derives from CodecBase and supplies the required members; the hooks have the
+// defaults below, and a codec that needs one declares a member of the same name, which hides the default (LookaheadDecoder calls
+// `codec_.x()` on the concrete type: no virtual call, no CRTP).
+//
+// Required of every codec:
+//   Sample, Params, Packet; Codec(const Params &); channels();
+//   decode_batch(ctx, batch, pcm)   one call of its own over the batch (a decoder without a Batcher, and the replay of one)
+//   packet_frames(i), plane_offset(c, i, k)   where packet i of the last batch of k lies in channel c's plane
+//   kBatchKind                      the SYMACCEL_BATCH_* kind of its submissions; 0 = it never goes through a Batcher
+// ... and, with kBatchKind != 0:
+//   batch_param(), batch_chains(k), batch_units(k)   the shape of a submission of k packets
+//   take_state(slot)                the batch that was waited for is now the current one: carried state out of the slot, layout kept
+//   fill_slot(batch, slot)          the parsed packets and the carried state into the page-locked slot -- for a codec whose layout depends
+//                                   on the packets' content (AacLcCoded, Vorbis, Flac, Adpcm, Pcm).  One with fixed-size units sets
+//   kDirect = true                  instead and supplies BatchView, view(slot, k), put(view, i, packet), extract(view, i), put_state(slot):
+//                                   LookaheadDecoder fills the slot itself, and a parser may write straight into it (LookaheadDecoder::Direct)
+// Everything else is a hook with a default:
+struct CodecBase {
+    template <class P>
+    static std::uint64_t id(const P &p) { return p.ts; }  // what identifies a packet: Packet::ts
+    void reset_state() {}       // AudioDecoder::reset: the carried state as after construction (default: nothing is carried)
+    void attach(Batcher &) {}   // once, when the decoder is made on a batcher: what the codec registers with it or reads from it
+    static constexpr bool kDirect = false;
+    struct BatchView {};        // (kDirect: where every plane of a batch of k lies, in a slot or in the codec's own vectors)
+    // set_output(): whether slot.out is the PCM the trait hands out as it comes back (false: take_state finishes it on the host)
+    bool device_output_is_final() const { return true; }
+    // A codec whose batcher kind delivers a format as [block][frame][channel] (ADPCM: the interleave group is one block's channels, the
+    // blocks of a packet follow one another; PCM) says so: publish() then finds a packet's bytes at its first block, set_output() refuses
+    // planar output, and `set_output_format(f)` tells the codec which of its two layouts plane_offset() is asked about
+    static constexpr bool kBlockInterleave = false;
+    void set_output_format(SampleFormat) {}
+    // A codec whose slot shape depends on the packets of the batch (PCM: the frames of its longest packet) is shown the batch before the
+    // slot is reserved: `prepare(batch)`
+    template <class B>
+    void prepare(const B &) {}
+    // ... and one whose plane 0 may go up as int16_t says so per batch, before the slot is reserved: `input_format(batch)` = 0 or
+    // SYMACCEL_FMT_S16 (symaccel_batcher_reserve_io); its fill_slot() then writes plane 0 in that format.  narrow_batches() /
+    // wide_batches(): the batches it submitted either way
+    template <class B>
+    int input_format(const B &) { return 0; }
+    std::size_t narrow_batches() const { return 0; }
+    std::size_t wide_batches() const { return 0; }
+    // A codec with no host parse stage (ADPCM) finds a packet's own errors -- a rejected preamble, a packet shorter than its blocks -- when
+    // the batch is assembled.  It keeps them per packet (`packet_error(i)`), the packet runs as silence, and decode() throws the error when
+    // THAT packet's turn comes: a packet fails alone (codecs/audio.rs:273-278), its neighbours in the look-ahead batch keep their PCM.
+    const Error *packet_error(std::size_t) const { return nullptr; }
+    // A codec that verifies its stream (FLAC: the STREAMINFO MD5) says so with `kVerifies` -- LookaheadDecoder::set_verify then refuses a
+    // change in mid-stream -- and is told about the decoder's life below it: `set_verify(bool)` (the registry's
+    // AudioDecoderOptions::verify), `published(i)` when packet i of the current batch is handed out, `rewind()` when whatever was computed
+    // beyond the last packet handed out is dropped (a seek, skipped packets, an error), `set_replaying(bool)` around the one-packet
+    // replay, which must not count, and `finalize_result()`: its verdict over the packets handed out (default: none, like the reference's
+    // decoders that verify nothing)
+    static constexpr bool kVerifies = false;
+    void set_verify(bool) {}
+    void published(std::size_t) {}
+    void rewind() {}
+    void set_replaying(bool) {}
+    FinalizeResult finalize_result() { return FinalizeResult{}; }
+
+    // Carried state: one plane = its host copy and its index in slot.state.  `state_planes()` of a codec lists them; put_state / take_state
+    // (and a fill_slot that writes its own) are store_state / load_state over that one list.
+    struct StatePlane {
+        void *host;
+        std::size_t bytes;
+        int index;
+    };
+    template <class T>
+    static StatePlane plane_of(std::vector<T> &v, int index) { return StatePlane{v.data(), v.size() * sizeof(T), index}; }
+    template <class Planes>
+    static void store_state(const Planes &planes, const symaccel_batch_slot &slot) {
+        for (const StatePlane &p : planes) std::memcpy(slot.state[p.index], p.host, p.bytes);
+    }
+    template <class Planes>
+    static void load_state(const Planes &planes, const symaccel_batch_slot &slot) {
+        for (const StatePlane &p : planes) std::memcpy(p.host, slot.state[p.index], p.bytes);
+    }
+};
 
 // With a `Batcher` (second constructor) the same decoder coalesces ACROSS streams: its batches are submitted to the process-wide
 // batcher instead of being transformed by a call of their own, and the next batch is submitted early -- as soon as half of the
@@ -731,13 +755,11 @@ public:
                 throw;
             }
         }
-        if constexpr (has_packet_errors<Codec>::value) {
-            if (const Error *e = codec_.packet_error(head_)) {
-                const Error own = *e;
-                ++head_;       // the packet is consumed: the rest of the batch stays
-                clear_last();  // audio.rs:278
-                throw own;
-            }
+        if (const Error *e = codec_.packet_error(head_)) {
+            const Error own = *e;
+            ++head_;       // the packet is consumed: the rest of the batch stays
+            clear_last();  // audio.rs:278
+            throw own;
         }
         publish(head_++);
         last_packet_ = packet;
@@ -757,16 +779,11 @@ public:
 
     // AudioDecoder::finalize (audio.rs:283-290): the codec's verdict over the packets handed out so far (the f32 codecs verify
     // nothing, like the reference's)
-    FinalizeResult finalize() {
-        if constexpr (has_finalize_result<Codec>::value) return codec_.finalize_result();
-        else return FinalizeResult{};
-    }
+    FinalizeResult finalize() { return codec_.finalize_result(); }
     // AudioDecoderOptions::verify for a codec that can (before the first decode()); the others behave as ever
     void set_verify(bool on) {
-        if constexpr (has_set_verify<Codec>::value) {
-            if (cur_live_ || next_live_ || head_ < ready_.size()) throw std::logic_error("LookaheadDecoder::set_verify: before the first decode()");
-            codec_.set_verify(on);
-        }
+        if (Codec::kVerifies && (cur_live_ || next_live_ || head_ < ready_.size())) throw std::logic_error("LookaheadDecoder::set_verify: before the first decode()");
+        codec_.set_verify(on);
     }
     const Buffer &last_decoded() const { return last_; }
     // Deliver the PCM in the caller's sample format, converted (and interleaved) in the batcher's scatter: what crosses the link is the
@@ -779,10 +796,10 @@ public:
             if (!batcher_ || Codec::kBatchKind == 0) throw std::invalid_argument("LookaheadDecoder::set_output: the conversion happens in the batcher's scatter");
             if (sample_bytes(format) == 0 || codec_.channels() > 8) throw std::invalid_argument("LookaheadDecoder::set_output: format / channels");
             if (!codec_.device_output_is_final()) throw Error(Error::Kind::Unsupported, SYMACCEL_ERR_UNSUPPORTED, "set_output: this stream's planes are finished on the host");
-            if (has_block_interleave<Codec>::value && !interleaved) throw Error(Error::Kind::Unsupported, SYMACCEL_ERR_UNSUPPORTED, "set_output: this codec's kernel writes interleaved frames");
+            if (Codec::kBlockInterleave && !interleaved) throw Error(Error::Kind::Unsupported, SYMACCEL_ERR_UNSUPPORTED, "set_output: this codec's kernel writes interleaved frames");
         }
         if (cur_live_ || next_live_ || head_ < ready_.size()) throw std::logic_error("LookaheadDecoder::set_output: between batches only (before decode() or after reset())");
-        if constexpr (has_block_interleave<Codec>::value) codec_.set_output_format(format);
+        codec_.set_output_format(format);
         out_fmt_ = format;
         out_interleaved_ = interleaved;
         clear_last();
@@ -791,14 +808,8 @@ public:
     std::size_t lookahead() const { return lookahead_; }
     std::size_t batches_run() const { return batches_; }
     // the batches this decoder submitted with plane 0 as int16_t / as int32_t (a codec with input_format(): Flac; 0 for the others)
-    std::size_t narrow_batches() const {
-        if constexpr (has_input_format<Codec>::value) return codec_.narrow_batches();
-        else return 0;
-    }
-    std::size_t wide_batches() const {
-        if constexpr (has_input_format<Codec>::value) return codec_.wide_batches();
-        else return 0;
-    }
+    std::size_t narrow_batches() const { return codec_.narrow_batches(); }
+    std::size_t wide_batches() const { return codec_.wide_batches(); }
 
 private:
     std::vector<Packet> gather(const Packet *first) {
@@ -840,13 +851,17 @@ private:
     void submit(const std::vector<Packet> &batch) {
         if constexpr (Codec::kBatchKind != 0) {
             symaccel_batch_slot slot;
-            if constexpr (has_prepare<Codec>::value) codec_.prepare(batch);
-            int in_fmt = 0;
-            if constexpr (has_input_format<Codec>::value) in_fmt = codec_.input_format(batch);
-            reserve(batch.size(), &slot, &next_ticket_, in_fmt);
+            codec_.prepare(batch);
+            reserve(batch.size(), &slot, &next_ticket_, codec_.input_format(batch));
             next_live_ = true;
-            try {
-                codec_.fill_slot(batch, slot);  // the parsed packets and the carried state go into the page-locked slot
+            try {  // the parsed packets and the carried state go into the page-locked slot
+                if constexpr (Codec::kDirect) {
+                    const typename Codec::BatchView view = codec_.view(slot, batch.size());
+                    for (std::size_t i = 0; i < batch.size(); ++i) codec_.put(view, i, batch[i]);
+                    codec_.put_state(slot);
+                } else {
+                    codec_.fill_slot(batch, slot);
+                }
             } catch (...) {
                 symaccel_batcher_release(batcher_->raw(), next_ticket_);
                 next_live_ = false;
@@ -858,30 +873,19 @@ private:
             hinted_ = false;
         }
     }
-    // a slot for a batch of n packets: the native planes, or (set_output) the interleave groups of the caller's format
+    // a slot for a batch of n packets: the native planes (SampleFormat::Native is out_fmt 0: the channel count is then not read), or
+    // (set_output) the interleave groups of the caller's format; in_fmt: plane 0 as int16_t, widened in the gather (input_format())
     void reserve(std::size_t n, symaccel_batch_slot *sl, std::uint64_t *t, int in_fmt = 0) {
-        if constexpr (Codec::kBatchKind != 0) {
-            if (in_fmt != 0)  // (a codec with input_format(): plane 0 as int16_t, widened in the gather)
-                batcher_->reserve_io(Codec::kBatchKind, codec_.batch_param(), codec_.batch_chains(n), codec_.batch_units(n), in_fmt,
-                                     out_fmt_ == SampleFormat::Native ? 0 : static_cast<int>(out_fmt_), out_interleaved_ ? (int)codec_.channels() : 1, sl, t);
-            else if (out_fmt_ == SampleFormat::Native)
-                check(symaccel_batcher_reserve(batcher_->raw(), Codec::kBatchKind, codec_.batch_param(), codec_.batch_chains(n), codec_.batch_units(n), sl, t), ctx_.raw());
-            else
-                check(symaccel_batcher_reserve_fmt(batcher_->raw(), Codec::kBatchKind, codec_.batch_param(), codec_.batch_chains(n), codec_.batch_units(n),
-                                                   static_cast<int>(out_fmt_), out_interleaved_ ? (int)codec_.channels() : 1, sl, t),
-                      ctx_.raw());
-        }
+        if constexpr (Codec::kBatchKind != 0)
+            batcher_->reserve_io(Codec::kBatchKind, codec_.batch_param(), codec_.batch_chains(n), codec_.batch_units(n), in_fmt, static_cast<int>(out_fmt_),
+                                 out_interleaved_ ? (int)codec_.channels() : 1, sl, t);
     }
     void replay_last() {
         std::vector<Packet> one(1, last_packet_);
         struct Replaying {  // (a verifying codec counts this packet once: when it was handed out)
             Codec &c;
-            explicit Replaying(Codec &codec) : c(codec) {
-                if constexpr (has_set_replaying<Codec>::value) c.set_replaying(true);
-            }
-            ~Replaying() {
-                if constexpr (has_set_replaying<Codec>::value) c.set_replaying(false);
-            }
+            explicit Replaying(Codec &codec) : c(codec) { c.set_replaying(true); }
+            ~Replaying() { c.set_replaying(false); }
         } replaying(codec_);
         if (batcher_) {
             if constexpr (Codec::kBatchKind != 0) {  // (through the batcher: the context is not ours to call while a batcher drives it)
@@ -985,7 +989,7 @@ private:
         }
     }
     void drop_tickets() {
-        if constexpr (has_rewind<Codec>::value) codec_.rewind();
+        codec_.rewind();
         if (!batcher_) return;
         if (next_live_) {
             symaccel_batcher_wait(batcher_->raw(), next_ticket_, nullptr);  // (its result is not wanted, its slot must be idle)
@@ -1006,7 +1010,7 @@ private:
         head_ = 0;
     }
     void publish(std::size_t i) {
-        if constexpr (has_published<Codec>::value) codec_.published(i);
+        codec_.published(i);
         // where packet i of the last batch lies in a channel's plane is the codec's business: fixed-size frames are
         // [channel][packet][frames]; Vorbis packs (prev_n + n) / 4 samples per packet and none for the first one
         const std::size_t nch = codec_.channels();
@@ -1025,7 +1029,7 @@ private:
                 bytes_.frames = last_.frames;
                 bytes_.channels = nch;
                 bytes_.format = out_fmt_;
-                if constexpr (has_block_interleave<Codec>::value) {
+                if constexpr (Codec::kBlockInterleave) {
                     bytes_.data = out_base_ + at0 * sb;  // (plane_offset(0, i) = the samples in front of the packet's first block, all channels)
                     bytes_.bytes = last_.frames * nch * sb;
                     bytes_.plane_stride = 0;
@@ -1077,7 +1081,7 @@ private:
 // AAC-LC: one packet = one raw_data_block = 1024 frames per channel.  What the CPU side (reference parser + spectral
 // tools) hands over per channel: the dequantised coefficients Ics::synth_channel would give Dsp::synth, the window
 // sequence and the window shapes (ics/mod.rs:449-468).
-struct AacLc {
+struct AacLc : CodecBase {
     using Sample = float;
     struct Params {
         std::size_t channels = 2;
@@ -1088,10 +1092,7 @@ struct AacLc {
         std::vector<std::uint8_t> side;      // [channel]: SYMACCEL_AAC_SIDE(seq, shape, prev_shape)
     };
     explicit AacLc(const Params &p) : nch_(p.channels), delay_(p.channels * 1024, 0.0f) {}
-    static std::uint64_t id(const Packet &p) { return p.ts; }
     std::size_t channels() const { return nch_; }
-    bool device_output_is_final() const { return true; }  // (set_output: slot.out is the PCM the trait hands out)
-    std::size_t frames_per_packet() const { return 1024; }
     std::size_t packet_frames(std::size_t) const { return 1024; }
     std::size_t plane_offset(std::size_t c, std::size_t i, std::size_t k) const { return (c * k + i) * 1024; }
     void reset_state() { std::fill(delay_.begin(), delay_.end(), 0.0f); }  // AacDecoder::reset: delay lines zeroed
@@ -1100,15 +1101,14 @@ struct AacLc {
         in_.resize(nch_ * k * 1024);
         side_.resize(nch_ * k);
         pcm.resize(nch_ * k * 1024);
-        gather(batch, in_.data(), side_.data());
+        const BatchView v{in_.data(), side_.data(), k, nch_};
+        for (std::size_t i = 0; i < k; ++i) put(v, i, batch[i]);
         check(symaccel_aac_synth(ctx.raw(), in_.data(), side_.data(), delay_.data(), pcm.data(), nch_, k), ctx.raw());
     }
     // the cross-stream batcher's view of the same batch (LookaheadDecoder's second constructor)
     static constexpr int kBatchKind = SYMACCEL_BATCH_AAC_SYNTH;
     static constexpr bool kDirect = true;
-    void attach(Batcher &) {}
     int batch_param() const { return 0; }
-    std::size_t units_per_packet() const { return 1; }
     std::size_t batch_chains(std::size_t) const { return nch_; }  // a submission of k packets: nch chains of k units
     std::size_t batch_units(std::size_t k) const { return k; }
     // where packet i of a batch of k lies in a slot's planes (what a parser that writes straight into the slot needs: LookaheadDecoder::Direct)
@@ -1122,9 +1122,9 @@ struct AacLc {
     BatchView view(const symaccel_batch_slot &slot, std::size_t k) const {
         return BatchView{static_cast<float *>(slot.input[0]), static_cast<std::uint8_t *>(slot.input[1]), k, nch_};
     }
-    void put(const BatchView &v, std::size_t i, const Packet &p) const {
-        if (p.coeffs.size() != nch_ * 1024 || p.side.size() != nch_) throw std::invalid_argument("AacLc: packet shape");
-        for (std::size_t c = 0; c < nch_; ++c) {
+    static void put(const BatchView &v, std::size_t i, const Packet &p) {  // (the one placement: a slot's planes or decode_batch's own)
+        if (p.coeffs.size() != v.nch * 1024 || p.side.size() != v.nch) throw std::invalid_argument("AacLc: packet shape");
+        for (std::size_t c = 0; c < v.nch; ++c) {
             std::copy_n(p.coeffs.data() + c * 1024, 1024, v.coeffs_at(c, i));
             v.side_at(c, i) = p.side[c];
         }
@@ -1139,25 +1139,11 @@ struct AacLc {
         }
         return p;
     }
-    void put_state(const symaccel_batch_slot &slot) const { std::memcpy(slot.state[0], delay_.data(), delay_.size() * sizeof(float)); }
-    void fill_slot(const std::vector<Packet> &batch, const symaccel_batch_slot &slot) {
-        const BatchView v = view(slot, batch.size());
-        for (std::size_t i = 0; i < batch.size(); ++i) put(v, i, batch[i]);
-        put_state(slot);
-    }
-    void take_state(const symaccel_batch_slot &slot) { std::memcpy(delay_.data(), slot.state[0], delay_.size() * sizeof(float)); }
+    std::array<StatePlane, 1> state_planes() { return {{plane_of(delay_, 0)}}; }
+    void put_state(const symaccel_batch_slot &slot) { store_state(state_planes(), slot); }
+    void take_state(const symaccel_batch_slot &slot) { load_state(state_planes(), slot); }
 
 private:
-    void gather(const std::vector<Packet> &batch, float *in, std::uint8_t *side) const {
-        const std::size_t k = batch.size();
-        for (std::size_t i = 0; i < k; ++i) {
-            if (batch[i].coeffs.size() != nch_ * 1024 || batch[i].side.size() != nch_) throw std::invalid_argument("AacLc: packet shape");
-            for (std::size_t c = 0; c < nch_; ++c) {
-                std::copy_n(batch[i].coeffs.data() + c * 1024, 1024, in + (c * k + i) * 1024);
-                side[c * k + i] = batch[i].side[c];
-            }
-        }
-    }
     std::size_t nch_;
     std::vector<float> delay_, in_;
     std::vector<std::uint8_t> side_;
@@ -1167,7 +1153,7 @@ private:
 // coefficients as decoded (mid / side or intensity coded where the descriptors say so), per jointly coded channel pair its
 // descriptor, and the TNS filters of the packet; joint stereo, TNS and Dsp::synth run on the device (symaccel_aac_decode_pipelined,
 // or SYMACCEL_BATCH_AAC_DECODE through the batcher: the pair frames with TNS take a list pass, the filters run, one walk synthesises).
-struct AacLcCoded {
+struct AacLcCoded : CodecBase {
     using Sample = float;
     struct Params {
         std::size_t channels = 2;
@@ -1183,9 +1169,7 @@ struct AacLcCoded {
     explicit AacLcCoded(const Params &p) : nch_(p.channels), swb_long_(p.swb_long), swb_short_(p.swb_short), delay_(p.channels * 1024, 0.0f) {
         if (swb_long_.size() < 2 || swb_short_.size() < 2) throw std::invalid_argument("AacLcCoded: band tables");
     }
-    static std::uint64_t id(const Packet &p) { return p.ts; }
     std::size_t channels() const { return nch_; }
-    bool device_output_is_final() const { return true; }  // (set_output: slot.out is the PCM the trait hands out)
     std::size_t packet_frames(std::size_t) const { return 1024; }
     std::size_t plane_offset(std::size_t c, std::size_t i, std::size_t k) const { return (c * k + i) * 1024; }
     void reset_state() { std::fill(delay_.begin(), delay_.end(), 0.0f); }
@@ -1201,15 +1185,12 @@ struct AacLcCoded {
                                             tns_.empty() ? nullptr : tns_.data(), tns_.size(), delay_.data(), pcm.data(), nch_, k, 0),
               ctx.raw());
     }
-    static constexpr int kBatchKind = SYMACCEL_BATCH_AAC_DECODE;
-    static constexpr bool kDirect = false;  // (the descriptor blob is assembled from the whole batch)
-    struct BatchView {};
+    static constexpr int kBatchKind = SYMACCEL_BATCH_AAC_DECODE;  // (not kDirect: the descriptor blob is assembled from the whole batch)
     void attach(Batcher &b) {
         check(symaccel_batcher_aac_bands(b.raw(), swb_long_.data(), (int)swb_long_.size() - 1, swb_short_.data(), (int)swb_short_.size() - 1, &bands_),
               b.context().raw());
     }
     int batch_param() const { return bands_; }
-    std::size_t units_per_packet() const { return 1; }
     std::size_t batch_chains(std::size_t) const { return nch_; }  // a submission of k packets: nch chains of k units
     std::size_t batch_units(std::size_t k) const { return k; }
     void fill_slot(const std::vector<Packet> &batch, const symaccel_batch_slot &slot) {
@@ -1228,9 +1209,10 @@ struct AacLcCoded {
             std::memcpy(blob + off_js, js_.data(), n_pairs * k * sizeof(symaccel_aac_js_frame));
         }
         if (!tns_.empty()) std::memcpy(blob + off_tns, tns_.data(), tns_.size() * sizeof(symaccel_aac_tns_filter));
-        std::memcpy(slot.state[0], delay_.data(), delay_.size() * sizeof(float));
+        store_state(state_planes(), slot);
     }
-    void take_state(const symaccel_batch_slot &slot) { std::memcpy(delay_.data(), slot.state[0], delay_.size() * sizeof(float)); }
+    std::array<StatePlane, 1> state_planes() { return {{plane_of(delay_, 0)}}; }
+    void take_state(const symaccel_batch_slot &slot) { load_state(state_planes(), slot); }
 
 private:
     // the batch in the entry points' terms: chain-major spectra + side bytes, the pairs coded jointly anywhere in the batch, their
@@ -1282,7 +1264,7 @@ private:
 // MPEG-1/2 Layer III: one packet = one frame = `granules` granules of 576 frames per channel (2 for MPEG-1, 1 for
 // MPEG-2 / 2.5, common.rs:173-178).  Per granule-channel: the requantised, stereo-processed samples and the side fields
 // the synthesis tail reads (layer3/mod.rs:440-476).
-struct Mp3 {
+struct Mp3 : CodecBase {
     using Sample = float;
     struct Params {
         std::size_t channels = 2;
@@ -1297,10 +1279,7 @@ struct Mp3 {
     explicit Mp3(const Params &p)
         : nch_(p.channels), ngr_(p.granules), sr_(p.sample_rate_idx), overlap_(p.channels * 576, 0.0f), vvec_(p.channels * 1024, 0.0f),
           vfront_(p.channels, 0) {}
-    static std::uint64_t id(const Packet &p) { return p.ts; }
     std::size_t channels() const { return nch_; }
-    bool device_output_is_final() const { return true; }  // (set_output: slot.out is the PCM the trait hands out)
-    std::size_t frames_per_packet() const { return 576 * ngr_; }
     std::size_t packet_frames(std::size_t) const { return 576 * ngr_; }
     std::size_t plane_offset(std::size_t c, std::size_t i, std::size_t k) const { return (c * k + i) * 576 * ngr_; }
     void reset_state() {  // MpaDecoder::reset: fresh State (overlap and SynthesisState::default())
@@ -1313,15 +1292,14 @@ struct Mp3 {
         in_.resize(nch_ * g * 576);
         side_.resize(nch_ * g);
         pcm.resize(nch_ * g * 576);
-        gather(batch, in_.data(), side_.data());
+        const BatchView v{in_.data(), side_.data(), k, nch_, ngr_};
+        for (std::size_t i = 0; i < k; ++i) put(v, i, batch[i]);
         check(symaccel_mp3_synth(ctx.raw(), in_.data(), side_.data(), sr_, overlap_.data(), vvec_.data(), vfront_.data(), pcm.data(), nch_, g),
               ctx.raw());
     }
     static constexpr int kBatchKind = SYMACCEL_BATCH_MP3_SYNTH;
     static constexpr bool kDirect = true;
-    void attach(Batcher &) {}
     int batch_param() const { return sr_; }
-    std::size_t units_per_packet() const { return ngr_; }
     std::size_t batch_chains(std::size_t) const { return nch_; }
     std::size_t batch_units(std::size_t k) const { return k * ngr_; }
     struct BatchView {  // granule gr of packet i of channel c is unit i * ngr + gr of chain c
@@ -1333,12 +1311,12 @@ struct Mp3 {
     BatchView view(const symaccel_batch_slot &slot, std::size_t k) const {
         return BatchView{static_cast<float *>(slot.input[0]), static_cast<symaccel_mp3_side *>(slot.input[1]), k, nch_, ngr_};
     }
-    void put(const BatchView &v, std::size_t i, const Packet &p) const {
-        if (p.xr.size() != ngr_ * nch_ * 576 || p.side.size() != ngr_ * nch_) throw std::invalid_argument("Mp3: packet shape");
-        for (std::size_t gr = 0; gr < ngr_; ++gr)
-            for (std::size_t c = 0; c < nch_; ++c) {
-                std::copy_n(p.xr.data() + (gr * nch_ + c) * 576, 576, v.xr + v.unit(c, i, gr) * 576);
-                v.side[v.unit(c, i, gr)] = p.side[gr * nch_ + c];
+    static void put(const BatchView &v, std::size_t i, const Packet &p) {
+        if (p.xr.size() != v.ngr * v.nch * 576 || p.side.size() != v.ngr * v.nch) throw std::invalid_argument("Mp3: packet shape");
+        for (std::size_t gr = 0; gr < v.ngr; ++gr)
+            for (std::size_t c = 0; c < v.nch; ++c) {
+                std::copy_n(p.xr.data() + (gr * v.nch + c) * 576, 576, v.xr + v.unit(c, i, gr) * 576);
+                v.side[v.unit(c, i, gr)] = p.side[gr * v.nch + c];
             }
     }
     Packet extract(const BatchView &v, std::size_t i) const {
@@ -1352,34 +1330,11 @@ struct Mp3 {
             }
         return p;
     }
-    void put_state(const symaccel_batch_slot &slot) const {
-        std::memcpy(slot.state[0], overlap_.data(), overlap_.size() * sizeof(float));
-        std::memcpy(slot.state[1], vvec_.data(), vvec_.size() * sizeof(float));
-        std::memcpy(slot.state[2], vfront_.data(), vfront_.size() * sizeof(std::int32_t));
-    }
-    void fill_slot(const std::vector<Packet> &batch, const symaccel_batch_slot &slot) {
-        const BatchView v = view(slot, batch.size());
-        for (std::size_t i = 0; i < batch.size(); ++i) put(v, i, batch[i]);
-        put_state(slot);
-    }
-    void take_state(const symaccel_batch_slot &slot) {
-        std::memcpy(overlap_.data(), slot.state[0], overlap_.size() * sizeof(float));
-        std::memcpy(vvec_.data(), slot.state[1], vvec_.size() * sizeof(float));
-        std::memcpy(vfront_.data(), slot.state[2], vfront_.size() * sizeof(std::int32_t));
-    }
+    std::array<StatePlane, 3> state_planes() { return {{plane_of(overlap_, 0), plane_of(vvec_, 1), plane_of(vfront_, 2)}}; }
+    void put_state(const symaccel_batch_slot &slot) { store_state(state_planes(), slot); }
+    void take_state(const symaccel_batch_slot &slot) { load_state(state_planes(), slot); }
 
 private:
-    void gather(const std::vector<Packet> &batch, float *in, symaccel_mp3_side *side) const {
-        const std::size_t k = batch.size(), g = k * ngr_;
-        for (std::size_t i = 0; i < k; ++i) {
-            if (batch[i].xr.size() != ngr_ * nch_ * 576 || batch[i].side.size() != ngr_ * nch_) throw std::invalid_argument("Mp3: packet shape");
-            for (std::size_t gr = 0; gr < ngr_; ++gr)
-                for (std::size_t c = 0; c < nch_; ++c) {
-                    std::copy_n(batch[i].xr.data() + (gr * nch_ + c) * 576, 576, in + (c * g + i * ngr_ + gr) * 576);
-                    side[c * g + i * ngr_ + gr] = batch[i].side[gr * nch_ + c];
-                }
-        }
-    }
     std::size_t nch_, ngr_;
     int sr_;
     std::vector<float> overlap_, vvec_, in_;
@@ -1392,7 +1347,7 @@ private:
 // layer2/mod.rs:262-318; include/symaccel.h, symaccel_mpa12_decode) -- handed to the fused kernel, which dequantises, scales and runs the
 // polyphase filterbank (layer1/mod.rs:142-194, layer2/mod.rs:320-384).  Two bytes per sample cross the link instead of four.  Chains are
 // independent (an intensity-coded sub-band simply has the same codes in both channels), so streams of any channel count share a launch.
-struct Mpa12 {
+struct Mpa12 : CodecBase {
     using Sample = float;
     struct Params {
         int layer = SYMACCEL_MPA_LAYER2;
@@ -1409,10 +1364,7 @@ struct Mpa12 {
         if (rb_ == 0) throw Error(Error::Kind::Unsupported, SYMACCEL_ERR_UNSUPPORTED, "mpa: invalid mpeg audio layer");
         if (nch_ < 1 || nch_ > 2) throw std::invalid_argument("Mpa12: one or two channels");
     }
-    static std::uint64_t id(const Packet &p) { return p.ts; }
     std::size_t channels() const { return nch_; }
-    bool device_output_is_final() const { return true; }
-    std::size_t frames_per_packet() const { return 32 * nf_; }
     std::size_t packet_frames(std::size_t) const { return 32 * nf_; }
     std::size_t plane_offset(std::size_t c, std::size_t i, std::size_t k) const { return (c * k + i) * 32 * nf_; }
     void reset_state() {  // MpaDecoder::reset: fresh State (SynthesisState::default(), decoder.rs:152-155)
@@ -1433,9 +1385,7 @@ struct Mpa12 {
     }
     static constexpr int kBatchKind = SYMACCEL_BATCH_MPA12_DECODE;
     static constexpr bool kDirect = true;
-    void attach(Batcher &) {}
     int batch_param() const { return layer_; }
-    std::size_t units_per_packet() const { return 1; }
     std::size_t batch_chains(std::size_t) const { return nch_; }
     std::size_t batch_units(std::size_t k) const { return k; }
     struct BatchView {  // packet i of channel c is unit i of chain c
@@ -1465,19 +1415,9 @@ struct Mpa12 {
         }
         return p;
     }
-    void put_state(const symaccel_batch_slot &slot) const {
-        std::memcpy(slot.state[0], vvec_.data(), vvec_.size() * sizeof(float));
-        std::memcpy(slot.state[1], vfront_.data(), vfront_.size() * sizeof(std::int32_t));
-    }
-    void fill_slot(const std::vector<Packet> &batch, const symaccel_batch_slot &slot) {
-        const BatchView v = view(slot, batch.size());
-        for (std::size_t i = 0; i < batch.size(); ++i) put(v, i, batch[i]);
-        put_state(slot);
-    }
-    void take_state(const symaccel_batch_slot &slot) {
-        std::memcpy(vvec_.data(), slot.state[0], vvec_.size() * sizeof(float));
-        std::memcpy(vfront_.data(), slot.state[1], vfront_.size() * sizeof(std::int32_t));
-    }
+    std::array<StatePlane, 2> state_planes() { return {{plane_of(vvec_, 0), plane_of(vfront_, 1)}}; }
+    void put_state(const symaccel_batch_slot &slot) { store_state(state_planes(), slot); }
+    void take_state(const symaccel_batch_slot &slot) { load_state(state_planes(), slot); }
 
 private:
     int layer_;
@@ -1492,7 +1432,7 @@ private:
 // int16, the GranuleChannel fields requantize reads, one stereo record per granule for a two-channel stream -- handed to
 // symaccel_mp3_decode_pipelined, which runs requantize + joint stereo + the synthesis tail on the device (layer3/mod.rs:421-477).
 // Half the bytes of Mp3's f32 spectra cross PCIe, and the host keeps neither POW43 nor the band loops.
-struct Mp3Huffman {
+struct Mp3Huffman : CodecBase {
     using Sample = float;
     struct Params {
         std::size_t channels = 2;  // 1, or 2 (one joint-stereo pair)
@@ -1511,9 +1451,7 @@ struct Mp3Huffman {
           vfront_(p.channels, 0) {
         if (p.channels < 1 || p.channels > 2) throw std::invalid_argument("Mp3Huffman: one or two channels");
     }
-    static std::uint64_t id(const Packet &p) { return p.ts; }
     std::size_t channels() const { return nch_; }
-    bool device_output_is_final() const { return true; }  // (set_output: slot.out is the PCM the trait hands out)
     std::size_t packet_frames(std::size_t) const { return 576 * ngr_; }
     std::size_t plane_offset(std::size_t c, std::size_t i, std::size_t k) const { return (c * k + i) * 576 * ngr_; }
     void reset_state() {
@@ -1528,18 +1466,17 @@ struct Mp3Huffman {
         side_.resize(nch_ * g);
         st_.resize(nch_ == 2 ? g : 0);
         pcm.resize(nch_ * g * 576);
-        gather(batch, q_.data(), rq_.data(), side_.data(), st_.data());
+        const BatchView v{q_.data(), rq_.data(), side_.data(), nch_ == 2 ? st_.data() : nullptr, k, nch_, ngr_};  // (mono: no stereo plane)
+        for (std::size_t i = 0; i < k; ++i) put(v, i, batch[i]);
         const std::int32_t pair[2] = {0, 1};
-        check(symaccel_mp3_decode_pipelined(ctx.raw(), q_.data(), rq_.data(), nch_ == 2 ? pair : nullptr, nch_ == 2 ? st_.data() : nullptr,
+        check(symaccel_mp3_decode_pipelined(ctx.raw(), q_.data(), rq_.data(), nch_ == 2 ? pair : nullptr, v.stereo,
                                             nch_ == 2 ? 1 : 0, side_.data(), sr_, overlap_.data(), vvec_.data(), vfront_.data(), pcm.data(), nch_, g, 0),
               ctx.raw());
     }
 
     static constexpr int kBatchKind = SYMACCEL_BATCH_MP3_DECODE;  // one stream per submission: exactly what this codec is
     static constexpr bool kDirect = true;
-    void attach(Batcher &) {}
     int batch_param() const { return sr_; }
-    std::size_t units_per_packet() const { return ngr_; }
     std::size_t batch_chains(std::size_t) const { return nch_; }
     std::size_t batch_units(std::size_t k) const { return k * ngr_; }
     struct BatchView {  // granule gr of packet i of channel c is unit i * ngr + gr of chain c; the stereo records are per granule of the STREAM
@@ -1554,18 +1491,19 @@ struct Mp3Huffman {
         return BatchView{static_cast<std::int16_t *>(slot.input[0]), static_cast<symaccel_mp3_requant *>(slot.input[1]),
                          static_cast<symaccel_mp3_side *>(slot.input[2]), static_cast<symaccel_mp3_stereo *>(slot.input[3]), k, nch_, ngr_};
     }
-    void put(const BatchView &v, std::size_t i, const Packet &p) const {
-        if (p.quant.size() != ngr_ * nch_ * 576 || p.rq.size() != ngr_ * nch_ || p.side.size() != ngr_ * nch_ || p.stereo.size() != (nch_ == 2 ? ngr_ : 0))
+    static void put(const BatchView &v, std::size_t i, const Packet &p) {
+        if (p.quant.size() != v.ngr * v.nch * 576 || p.rq.size() != v.ngr * v.nch || p.side.size() != v.ngr * v.nch || p.stereo.size() != (v.nch == 2 ? v.ngr : 0))
             throw std::invalid_argument("Mp3Huffman: packet shape");
-        for (std::size_t gr = 0; gr < ngr_; ++gr) {
-            for (std::size_t c = 0; c < nch_; ++c) {
+        for (std::size_t gr = 0; gr < v.ngr; ++gr) {
+            for (std::size_t c = 0; c < v.nch; ++c) {
                 const std::size_t dst = v.unit(c, i, gr);
-                std::copy_n(p.quant.data() + (gr * nch_ + c) * 576, 576, v.quant + dst * 576);
-                v.rq[dst] = p.rq[gr * nch_ + c];
-                v.side[dst] = p.side[gr * nch_ + c];
+                std::copy_n(p.quant.data() + (gr * v.nch + c) * 576, 576, v.quant + dst * 576);
+                v.rq[dst] = p.rq[gr * v.nch + c];
+                v.side[dst] = p.side[gr * v.nch + c];
             }
-            if (nch_ == 2) v.stereo[i * ngr_ + gr] = p.stereo[gr];
-            else std::memset(&v.stereo[i * ngr_ + gr], 0, sizeof(symaccel_mp3_stereo));
+            // a mono stream has no stereo records: a slot's plane (it has one whatever the channel count) stays zeroed, decode_batch has none
+            if (v.nch == 2) v.stereo[i * v.ngr + gr] = p.stereo[gr];
+            else if (v.stereo) std::memset(&v.stereo[i * v.ngr + gr], 0, sizeof(symaccel_mp3_stereo));
         }
     }
     Packet extract(const BatchView &v, std::size_t i) const {
@@ -1585,41 +1523,11 @@ struct Mp3Huffman {
         }
         return p;
     }
-    void put_state(const symaccel_batch_slot &slot) const {
-        std::memcpy(slot.state[0], overlap_.data(), overlap_.size() * sizeof(float));
-        std::memcpy(slot.state[1], vvec_.data(), vvec_.size() * sizeof(float));
-        std::memcpy(slot.state[2], vfront_.data(), vfront_.size() * sizeof(std::int32_t));
-    }
-    void fill_slot(const std::vector<Packet> &batch, const symaccel_batch_slot &slot) {
-        const BatchView v = view(slot, batch.size());
-        for (std::size_t i = 0; i < batch.size(); ++i) put(v, i, batch[i]);
-        put_state(slot);
-    }
-    void take_state(const symaccel_batch_slot &slot) {
-        std::memcpy(overlap_.data(), slot.state[0], overlap_.size() * sizeof(float));
-        std::memcpy(vvec_.data(), slot.state[1], vvec_.size() * sizeof(float));
-        std::memcpy(vfront_.data(), slot.state[2], vfront_.size() * sizeof(std::int32_t));
-    }
+    std::array<StatePlane, 3> state_planes() { return {{plane_of(overlap_, 0), plane_of(vvec_, 1), plane_of(vfront_, 2)}}; }
+    void put_state(const symaccel_batch_slot &slot) { store_state(state_planes(), slot); }
+    void take_state(const symaccel_batch_slot &slot) { load_state(state_planes(), slot); }
 
 private:
-    void gather(const std::vector<Packet> &batch, std::int16_t *q, symaccel_mp3_requant *rq, symaccel_mp3_side *side, symaccel_mp3_stereo *st) const {
-        const std::size_t k = batch.size(), g = k * ngr_;
-        for (std::size_t i = 0; i < k; ++i) {
-            const Packet &p = batch[i];
-            if (p.quant.size() != ngr_ * nch_ * 576 || p.rq.size() != ngr_ * nch_ || p.side.size() != ngr_ * nch_ ||
-                p.stereo.size() != (nch_ == 2 ? ngr_ : 0))
-                throw std::invalid_argument("Mp3Huffman: packet shape");
-            for (std::size_t gr = 0; gr < ngr_; ++gr) {
-                for (std::size_t c = 0; c < nch_; ++c) {
-                    const std::size_t dst = c * g + i * ngr_ + gr;
-                    std::copy_n(p.quant.data() + (gr * nch_ + c) * 576, 576, q + dst * 576);
-                    rq[dst] = p.rq[gr * nch_ + c];
-                    side[dst] = p.side[gr * nch_ + c];
-                }
-                if (nch_ == 2) st[i * ngr_ + gr] = p.stereo[gr];
-            }
-        }
-    }
     std::size_t nch_, ngr_;
     int sr_;
     std::vector<float> overlap_, vvec_;
@@ -1634,7 +1542,7 @@ private:
 // channel: floor x residue, the n / 2 lines DspChannel::synth receives (lib.rs:282-331).  A packet yields
 // (prev_n + n) / 4 frames -- none for the first block after a reset (dsp.rs:77-80) -- so the batch's PCM is packed
 // (include/symaccel.h, "Vorbis") and the per-packet spans are what publish() asks for.
-struct Vorbis {
+struct Vorbis : CodecBase {
     using Sample = float;
     struct Params {
         std::size_t channels = 2;
@@ -1647,9 +1555,7 @@ struct Vorbis {
     };
     explicit Vorbis(const Params &p)
         : nch_(p.channels), e0_(p.bs0_exp), e1_(p.bs1_exp), prev_(p.channels, -1), overlap_(p.channels * ((std::size_t)1 << (p.bs1_exp - 1)), 0.0f) {}
-    static std::uint64_t id(const Packet &p) { return p.ts; }
     std::size_t channels() const { return nch_; }
-    bool device_output_is_final() const { return true; }  // (set_output: slot.out is the PCM the trait hands out)
     std::size_t packet_frames(std::size_t i) const { return emits_[i] ? off_[i + 1] - off_[i] : 0; }
     std::size_t plane_offset(std::size_t c, std::size_t i, std::size_t) const { return c * stride_ + off_[i]; }
     void reset_state() {  // Dsp::reset (dsp.rs:45-56): no block to lap with, overlap zeroed
@@ -1671,12 +1577,8 @@ struct Vorbis {
     }
     // the cross-stream batcher's view: every chain's planes at their largest (k * bs1 / 2), the packed data at the front -- so that
     // streams with different block flags share a launch (SYMACCEL_BATCH_VORBIS_SYNTH)
-    static constexpr int kBatchKind = SYMACCEL_BATCH_VORBIS_SYNTH;
-    static constexpr bool kDirect = false;  // (the packed layout depends on every packet's block flag)
-    struct BatchView {};
-    void attach(Batcher &) {}
+    static constexpr int kBatchKind = SYMACCEL_BATCH_VORBIS_SYNTH;  // (not kDirect: the packed layout depends on every packet's block flag)
     int batch_param() const { return e0_ | (e1_ << 8); }
-    std::size_t units_per_packet() const { return 1; }
     std::size_t batch_chains(std::size_t) const { return nch_; }  // a submission of k packets: nch chains of k units
     std::size_t batch_units(std::size_t k) const { return k; }
     void fill_slot(const std::vector<Packet> &batch, const symaccel_batch_slot &slot) {
@@ -1696,12 +1598,11 @@ struct Vorbis {
         off_.swap(cur_off);
         spec_off_.swap(cur_spec);
         emits_.swap(cur_emits);
-        std::memcpy(slot.state[0], prev_.data(), prev_.size() * sizeof(std::int32_t));
-        std::memcpy(slot.state[1], overlap_.data(), overlap_.size() * sizeof(float));
+        store_state(state_planes(), slot);
     }
+    std::array<StatePlane, 2> state_planes() { return {{plane_of(prev_, 0), plane_of(overlap_, 1)}}; }
     void take_state(const symaccel_batch_slot &slot) {
-        std::memcpy(prev_.data(), slot.state[0], prev_.size() * sizeof(std::int32_t));
-        std::memcpy(overlap_.data(), slot.state[1], overlap_.size() * sizeof(float));
+        load_state(state_planes(), slot);
         off_.swap(next_off_);
         emits_.swap(next_emits_);
         stride_ = next_stride_;
@@ -1759,7 +1660,7 @@ private:
 // (decoder.rs:663-752), then the stereo decorrelation and the `<< (32 - bps)` of decoder.rs:199-242.  FLAC carries no
 // state from frame to frame, so reset() has nothing to zero; block sizes may differ from packet to packet (the last
 // frame; variable-block-size streams): every subframe gets a slot of the batch's largest block size.
-struct Flac {
+struct Flac : CodecBase {
     using Sample = std::int32_t;
     struct Params {
         std::size_t channels = 2;
@@ -1816,8 +1717,7 @@ struct Flac {
     // every other layout the plain one with the shift on the host.  Verifying, the same split: 0x300 | shift (the finishing MD5 kernel
     // leaves the pair decorrelated and left-justified) for two channels, 0x200 otherwise.
     static constexpr int kBatchKind = SYMACCEL_BATCH_FLAC_RESTORE;
-    static constexpr bool kDirect = false;
-    struct BatchView {};
+    static constexpr bool kVerifies = true;
     void attach(Batcher &b) { narrow_ok_ = b.narrow_input(); }
     // The input format of a batch (LookaheadDecoder asks before it reserves: the format belongs to the reservation): int16_t when EVERY
     // warm-up sample and residual of the batch fits -- the 16-bit streams, but for a side channel's 17-bit warm-up here and there --, else
@@ -1847,9 +1747,7 @@ struct Flac {
         next_lens_.assign(k, 0);
         for (std::size_t i = 0; i < k; ++i) {
             const Packet &p = batch[i];
-            if (p.blocksize == 0 || p.blocksize > max_bs_ || p.words.size() != nch_ * p.blocksize || p.desc.size() != nch_ || p.coeffs.size() != nch_ * 32 ||
-                p.pair_mode > 3 || (p.pair_mode != 0 && nch_ != 2))
-                throw std::invalid_argument("Flac: packet shape");
+            check_shape(p, max_bs_);
             next_lens_[i] = p.blocksize;
             for (std::size_t c = 0; c < nch_; ++c) {
                 if (narrow_next_) {  // (input_format() found that every word fits: packed straight into the slot)
@@ -1884,21 +1782,17 @@ struct Flac {
             for (std::size_t i = 0; i < slot.out_bytes / 4; ++i) words[i] = (std::int32_t)((std::uint32_t)words[i] << shift_);
         }
     }
-    static std::uint64_t id(const Packet &p) { return p.ts; }
     std::size_t channels() const { return nch_; }
     bool device_output_is_final() const { return nch_ == 2; }  // (set_output: other layouts are left-justified on the host, take_state)
     std::size_t packet_frames(std::size_t i) const { return lens_[i]; }
     std::size_t plane_offset(std::size_t c, std::size_t i, std::size_t) const { return (i * nch_ + c) * stride_; }
-    void reset_state() {}
     void decode_batch(Context &ctx, const std::vector<Packet> &batch, std::vector<std::int32_t> &pcm) {
         const std::size_t k = batch.size();
         stride_ = 0;
         lens_.assign(k, 0);
         for (std::size_t i = 0; i < k; ++i) {
             const Packet &p = batch[i];
-            if (p.blocksize == 0 || p.blocksize > 65535 || p.words.size() != nch_ * p.blocksize || p.desc.size() != nch_ ||
-                p.coeffs.size() != nch_ * 32 || p.pair_mode > 3 || (p.pair_mode != 0 && nch_ != 2))
-                throw std::invalid_argument("Flac: packet shape");
+            check_shape(p, 65535);
             lens_[i] = p.blocksize;
             stride_ = std::max(stride_, p.blocksize);
         }
@@ -1943,6 +1837,12 @@ struct Flac {
     }
 
 private:
+    // a packet's shape; `limit`: the longest block its destination takes (the slot's rows with the batcher, the block-size field without)
+    void check_shape(const Packet &p, std::size_t limit) const {
+        if (p.blocksize == 0 || p.blocksize > limit || p.words.size() != nch_ * p.blocksize || p.desc.size() != nch_ || p.coeffs.size() != nch_ * 32 ||
+            p.pair_mode > 3 || (p.pair_mode != 0 && nch_ != 2))
+            throw std::invalid_argument("Flac: packet shape");
+    }
     bool hashing() const { return verify_ && !replaying_; }
     unsigned bytes_per_sample() const { return (32u - shift_ + 7) / 8; }  // validate.rs:39-45
     symaccel_flac_md5_frame md5_frame(const Packet &p) const {
@@ -1973,7 +1873,7 @@ private:
 // codec, channel count and block size share launches.  The device writes pcm[block][channel][fpb]; the trait's planes are
 // [channel][block * fpb + frame], so a stereo packet of several blocks is re-packed in the slot on the host (take_state).  A delivered
 // format needs no re-pack: the kernel writes [block][frame][channel] and a packet's blocks follow one another.
-struct Adpcm {
+struct Adpcm : CodecBase {
     using Sample = std::int32_t;
     struct Params {
         int codec = SYMACCEL_ADPCM_MS;  // SYMACCEL_ADPCM_*
@@ -1994,10 +1894,7 @@ struct Adpcm {
         if (bpp_ == 0) throw Error(Error::Kind::Unsupported, SYMACCEL_ERR_UNSUPPORTED, "adpcm: maximum frames per packet is required");
     }
     static constexpr int kBatchKind = SYMACCEL_BATCH_ADPCM_DECODE;
-    static constexpr bool kDirect = false;
     static constexpr bool kBlockInterleave = true;
-    struct BatchView {};
-    void attach(Batcher &) {}
     void set_output_format(SampleFormat f) { native_ = f == SampleFormat::Native; }
     int batch_param() const { return codec_ | (int)(nch_ << 8); }
     std::size_t batch_chains(std::size_t k) const { return k * bpp_; }
@@ -2049,13 +1946,10 @@ struct Adpcm {
         stride_ = bpp_;
         if (native_ && nch_ == 2 && bpp_ > 1) repack(static_cast<std::int32_t *>(slot.out), blocks_.size(), bpp_);
     }
-    static std::uint64_t id(const Packet &p) { return p.ts; }
     std::size_t channels() const { return nch_; }
-    bool device_output_is_final() const { return true; }
     std::size_t packet_frames(std::size_t i) const { return blocks_[i] * fpb_; }
     // native: packet i's channel c is [block * fpb + frame] at (i * nch + c) * stride * fpb; a format: channel 0 names the packet's first sample
     std::size_t plane_offset(std::size_t c, std::size_t i, std::size_t) const { return (i * nch_ + (native_ ? c : 0)) * stride_ * fpb_; }
-    void reset_state() {}
     void decode_batch(Context &ctx, const std::vector<Packet> &batch, std::vector<std::int32_t> &pcm) {
         const std::size_t k = batch.size();
         blocks_.assign(k, 0);
@@ -2102,7 +1996,7 @@ private:
 //
 // The native planes are the reference's buffer sample type as Rust holds it (symaccel_pcm_native_bytes: 1, 2, 4 or 8 bytes; i24 / u24 in a
 // 32-bit word), so Sample is a byte: `planes[c]` points at `frames * native_bytes()` bytes, to be read as variant()'s type.
-struct Pcm {
+struct Pcm : CodecBase {
     using Sample = std::uint8_t;
     struct Params {  // AudioCodecParameters (codecs/audio.rs:300-400): what PcmDecoder::try_new reads
         int codec = SYMACCEL_PCM_S16LE;  // SYMACCEL_PCM_*; anything else is a codec the reference's decoder does not take either
@@ -2143,10 +2037,7 @@ struct Pcm {
         if (nch_ > 8 || (!implicit && shift_ == width)) throw unsupported("pcm: a shape the device decoder refuses");
     }
     static constexpr int kBatchKind = SYMACCEL_BATCH_PCM_DECODE;
-    static constexpr bool kDirect = false;
     static constexpr bool kBlockInterleave = true;  // (a format leaves the kernel as [packet][frame][channel])
-    struct BatchView {};
-    void attach(Batcher &) {}
     void set_output_format(SampleFormat f) { native_ = f == SampleFormat::Native; }
     int batch_param() const { return codec_ | (int)(nch_ << 8) | (int)(shift_ << 16); }
     std::size_t batch_chains(std::size_t k) const { return k; }
@@ -2167,15 +2058,12 @@ struct Pcm {
         frames_.swap(next_frames_);
         units_ = next_units_;
     }
-    static std::uint64_t id(const Packet &p) { return p.ts; }
     std::size_t channels() const { return nch_; }
-    bool device_output_is_final() const { return true; }
     std::size_t packet_frames(std::size_t i) const { return frames_[i]; }
     // native: BYTES in front of packet i's channel c in [packet][channel][units]; a format: the samples in front of the packet, all channels
     std::size_t plane_offset(std::size_t c, std::size_t i, std::size_t) const {
         return native_ ? (i * nch_ + c) * units_ * native_bytes_ : i * units_ * nch_;
     }
-    void reset_state() {}
     void decode_batch(Context &ctx, const std::vector<Packet> &batch, std::vector<std::uint8_t> &pcm) {
         prepare(batch);
         units_ = next_units_;
@@ -2232,7 +2120,7 @@ public:
                                                                 typename LookaheadDecoder<Codec>::Peek peek) const {
         require<Codec>();
         auto dec = std::make_unique<LookaheadDecoder<Codec>>(Batcher::shared(), params, opts.lookahead, std::move(peek));
-        if (opts.verify) dec->set_verify(true);  // (a codec without set_verify decodes as ever: the reference's verify nothing either)
+        if (opts.verify) dec->set_verify(true);  // (a codec that does not verify decodes as ever: the reference's verify nothing either)
         return dec;
     }
     // (zero-copy parse, for the codecs with kDirect)

@@ -164,27 +164,28 @@ static void test_mp3(Context &ctx, size_t lookahead, Batcher *batcher = nullptr)
 }
 
 // ---- MP3 one stage earlier: int16 Huffman samples + records in, the device requantises and runs the joint stereo
-static void test_mp3_huffman(Context &ctx, size_t lookahead, Batcher *batcher = nullptr) {
-    const size_t nch = 2, ngr = 2, n = 19;
-    const int sr = 0;
-    std::mt19937 rng(501 + (unsigned)lookahead);
+// (a mono stream carries no stereo records and its side records keep the channel's own rzero)
+static std::vector<Mp3Huffman::Packet> mp3h_track(size_t n, size_t nch, size_t ngr, unsigned seed) {
+    std::mt19937 rng(seed);
     std::vector<Mp3Huffman::Packet> track(n);
     for (size_t i = 0; i < n; ++i) {
         Mp3Huffman::Packet &p = track[i];
         p.ts = 7000 + 1152 * i;
         p.quant.resize(ngr * nch * 576);
         p.rq.resize(ngr * nch);
-        p.stereo.resize(ngr);
+        p.stereo.resize(nch == 2 ? ngr : 0);
         p.side.resize(ngr * nch);
         for (size_t gr = 0; gr < ngr; ++gr) {
             const unsigned rz0 = 2 * (unsigned)(rng() % 289), rz1 = 2 * (unsigned)(rng() % 289);
-            const unsigned flags = (unsigned)(rng() % 4) | SYMACCEL_MP3_ST_MPEG1;
-            symaccel_mp3_stereo &sd = p.stereo[gr];
-            std::memset(&sd, 0, sizeof sd);
-            sd.flags = (uint8_t)flags;
-            sd.rzero0 = (uint16_t)rz0;
-            sd.rzero1 = (uint16_t)rz1;
-            for (int s = 0; s < 39; ++s) sd.scalefacs1[s] = (uint8_t)(rng() % 8);
+            const unsigned flags = nch == 2 ? (unsigned)(rng() % 4) | SYMACCEL_MP3_ST_MPEG1 : 0u;
+            if (nch == 2) {
+                symaccel_mp3_stereo &sd = p.stereo[gr];
+                std::memset(&sd, 0, sizeof sd);
+                sd.flags = (uint8_t)flags;
+                sd.rzero0 = (uint16_t)rz0;
+                sd.rzero1 = (uint16_t)rz1;
+                for (int s = 0; s < 39; ++s) sd.scalefacs1[s] = (uint8_t)(rng() % 8);
+            }
             const unsigned end = rz0 > rz1 ? rz0 : rz1;
             for (size_t c = 0; c < nch; ++c) {
                 const unsigned rz = c == 0 ? rz0 : rz1;
@@ -200,6 +201,41 @@ static void test_mp3_huffman(Context &ctx, size_t lookahead, Batcher *batcher = 
             }
         }
     }
+    return track;
+}
+
+struct Mp3HuffmanOracle {  // a frame-by-frame decoder: requantize, stereo and the synthesis tail granule by granule (layer3/mod.rs:421-477)
+    size_t nch, ngr;
+    int sr;
+    std::vector<float> ov, vv;
+    std::vector<int32_t> vf;
+    Mp3HuffmanOracle(size_t c, size_t g, int sr_idx) : nch(c), ngr(g), sr(sr_idx), ov(c * 576, 0.0f), vv(c * 1024, 0.0f), vf(c, 0) {}
+    void reset() {
+        std::fill(ov.begin(), ov.end(), 0.0f);
+        std::fill(vv.begin(), vv.end(), 0.0f);
+        std::fill(vf.begin(), vf.end(), 0);
+    }
+    std::vector<float> decode(const Mp3Huffman::Packet &p) {  // [channel][576 * ngr]
+        std::vector<float> pcm(nch * 576 * ngr);
+        for (size_t gr = 0; gr < ngr; ++gr) {
+            float xr[2][576];
+            for (size_t c = 0; c < nch; ++c)
+                so_mp3_requantize(p.quant.data() + (gr * nch + c) * 576, reinterpret_cast<const so_mp3_requant *>(&p.rq[gr * nch + c]), sr, xr[c]);
+            if (nch == 2) so_mp3_stereo(xr[0], xr[1], reinterpret_cast<const so_mp3_stereo_desc *>(&p.stereo[gr]), sr);
+            for (size_t c = 0; c < nch; ++c) {
+                const symaccel_mp3_side &sd = p.side[gr * nch + c];
+                const uint8_t side[4] = {sd.block_type, sd.is_mixed, (uint8_t)(sd.rzero & 255), (uint8_t)(sd.rzero >> 8)};
+                so_mp3_synth_batch(xr[c], side, sr, ov.data() + c * 576, vv.data() + c * 1024, &vf[c], pcm.data() + (c * ngr + gr) * 576, 1, 1);
+            }
+        }
+        return pcm;
+    }
+};
+
+static void test_mp3_huffman(Context &ctx, size_t lookahead, Batcher *batcher = nullptr) {
+    const size_t nch = 2, ngr = 2, n = 19;
+    const int sr = 0;
+    auto track = mp3h_track(n, nch, ngr, 501 + (unsigned)lookahead);
     size_t cursor = 0;
     auto peek = [&]() -> std::optional<Mp3Huffman::Packet> {
         if (cursor >= track.size()) return std::nullopt;
@@ -209,33 +245,59 @@ static void test_mp3_huffman(Context &ctx, size_t lookahead, Batcher *batcher = 
     if (batcher) holder.emplace(*batcher, Mp3Huffman::Params{nch, ngr, sr}, lookahead, peek);
     else holder.emplace(ctx, Mp3Huffman::Params{nch, ngr, sr}, lookahead, peek);
     LookaheadDecoder<Mp3Huffman> &dec = *holder;
-    std::vector<float> ov(nch * 576, 0.0f), vv(nch * 1024, 0.0f);
-    std::vector<int32_t> vf(nch, 0);
+    Mp3HuffmanOracle ref(nch, ngr, sr);
     for (size_t i = 0; i < n; ++i) {
         if (i == 8) {  // seek
             dec.reset();
-            std::fill(ov.begin(), ov.end(), 0.0f);
-            std::fill(vv.begin(), vv.end(), 0.0f);
-            std::fill(vf.begin(), vf.end(), 0);
+            ref.reset();
             cursor = i;
         }
         if (cursor <= i) cursor = i + 1;
         const AudioBufferRef &buf = dec.decode(track[i]);
-        const Mp3Huffman::Packet &p = track[i];
-        float want[2][1152];
-        for (size_t gr = 0; gr < ngr; ++gr) {
-            float xr[2][576];
-            for (size_t c = 0; c < nch; ++c)
-                so_mp3_requantize(p.quant.data() + (gr * nch + c) * 576, reinterpret_cast<const so_mp3_requant *>(&p.rq[gr * nch + c]), sr, xr[c]);
-            so_mp3_stereo(xr[0], xr[1], reinterpret_cast<const so_mp3_stereo_desc *>(&p.stereo[gr]), sr);
-            for (size_t c = 0; c < nch; ++c) {
-                const symaccel_mp3_side &sd = p.side[gr * nch + c];
-                const uint8_t side[4] = {sd.block_type, sd.is_mixed, (uint8_t)(sd.rzero & 255), (uint8_t)(sd.rzero >> 8)};
-                so_mp3_synth_batch(xr[c], side, sr, ov.data() + c * 576, vv.data() + c * 1024, &vf[c], want[c] + gr * 576, 1, 1);
-            }
-        }
+        const std::vector<float> want = ref.decode(track[i]);
         for (size_t c = 0; c < nch; ++c)
-            EXPECT(same_bits(buf.planes[c], want[c], 1152), "MP3 (Huffman in) K=%zu packet %zu channel %zu differs from the frame-by-frame decoder", lookahead, i, c);
+            EXPECT(same_bits(buf.planes[c], want.data() + c * 1152, 1152), "MP3 (Huffman in) K=%zu packet %zu channel %zu differs from the frame-by-frame decoder", lookahead, i, c);
+    }
+}
+
+// Mono and stereo, MPEG-1 (two granules) and MPEG-2 (one), through Mp3Huffman's one placement: 3 packets at look-ahead 2 -- one batch
+// boundary -- by a decoder of its own (decode_batch: planes of its own, no stereo plane for mono) and on a Batcher (the slot, whose
+// stereo plane is there whatever the channel count).  Both equal each other and the frame-by-frame decoder.
+static void test_mp3_huffman_shapes(Context &ctx, size_t nch, size_t ngr) {
+    const size_t n = 3, lookahead = 2, frames = 576 * ngr;
+    const int sr = ngr == 2 ? 0 : 3;
+    const auto track = mp3h_track(n, nch, ngr, 900 + (unsigned)(10 * nch + ngr));
+    Mp3HuffmanOracle ref(nch, ngr, sr);
+    std::vector<std::vector<float>> want;
+    for (const auto &p : track) want.push_back(ref.decode(p));
+    auto run = [&](Batcher *batcher) {
+        size_t cursor = 0;
+        auto peek = [&]() -> std::optional<Mp3Huffman::Packet> {
+            if (cursor >= track.size()) return std::nullopt;
+            return track[cursor++];
+        };
+        std::optional<LookaheadDecoder<Mp3Huffman>> dec;
+        if (batcher) dec.emplace(*batcher, Mp3Huffman::Params{nch, ngr, sr}, lookahead, peek);
+        else dec.emplace(ctx, Mp3Huffman::Params{nch, ngr, sr}, lookahead, peek);
+        std::vector<std::vector<float>> got;
+        for (size_t i = 0; i < n; ++i) {
+            if (cursor <= i) cursor = i + 1;
+            const AudioBufferRef &buf = dec->decode(track[i]);
+            EXPECT(buf.frames == frames && buf.planes.size() == nch, "MP3 (Huffman in) %zu ch %zu gr: buffer shape at packet %zu", nch, ngr, i);
+            got.emplace_back();
+            for (size_t c = 0; c < nch && buf.frames == frames; ++c) got.back().insert(got.back().end(), buf.planes[c], buf.planes[c] + frames);
+        }
+        EXPECT(dec->batches_run() == 2, "MP3 (Huffman in) %zu ch %zu gr: %zu batches, expected 2", nch, ngr, dec->batches_run());
+        return got;
+    };
+    const auto own = run(nullptr);
+    Batcher batcher(ctx);
+    const auto pooled = run(&batcher);
+    for (size_t i = 0; i < n; ++i) {
+        const bool whole = own[i].size() == nch * frames && pooled[i].size() == nch * frames;
+        EXPECT(whole && same_bits(own[i].data(), pooled[i].data(), nch * frames), "MP3 (Huffman in) %zu ch %zu gr packet %zu: the decoder of its own and the one on a batcher differ", nch, ngr, i);
+        EXPECT(whole && same_bits(own[i].data(), want[i].data(), nch * frames), "MP3 (Huffman in) %zu ch %zu gr packet %zu: decode_batch differs from the frame-by-frame decoder", nch, ngr, i);
+        EXPECT(whole && same_bits(pooled[i].data(), want[i].data(), nch * frames), "MP3 (Huffman in) %zu ch %zu gr packet %zu: the batcher differs from the frame-by-frame decoder", nch, ngr, i);
     }
 }
 
@@ -564,6 +626,9 @@ int main(int argc, char **argv) {
         test_flac(ctx, 5, 1, 24, &batcher);
         test_flac(ctx, 7, 3, 20, &batcher);
     }
+    test_mp3_huffman_shapes(ctx, 1, 2);
+    test_mp3_huffman_shapes(ctx, 1, 1);
+    test_mp3_huffman_shapes(ctx, 2, 2);
     test_cross_stream(ctx, 1, 8);
     test_cross_stream(ctx, 7, 8);
     test_cross_stream(ctx, 16, 3);

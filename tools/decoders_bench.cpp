@@ -198,38 +198,6 @@ std::vector<AacLcCoded::Packet> make_pool<AacLcCoded>(unsigned seed) {  // long 
     return pool;
 }
 
-// --direct: the "parser" writes the next packet straight into the batcher's slot (LookaheadDecoder::Direct) -- one copy of the
-// parsed packet (pool -> slot) instead of two (pool -> Packet -> slot)
-template <class Codec>
-void parse_into(const typename Codec::BatchView &, std::size_t, const typename Codec::Packet &) {}
-template <>
-void parse_into<AacLc>(const AacLc::BatchView &v, std::size_t i, const AacLc::Packet &p) {
-    for (size_t c = 0; c < v.nch; ++c) {
-        std::memcpy(v.coeffs_at(c, i), p.coeffs.data() + c * 1024, 4096);
-        v.side_at(c, i) = p.side[c];
-    }
-}
-template <>
-void parse_into<Mp3>(const Mp3::BatchView &v, std::size_t i, const Mp3::Packet &p) {
-    for (size_t gr = 0; gr < v.ngr; ++gr)
-        for (size_t c = 0; c < v.nch; ++c) {
-            std::memcpy(v.xr + v.unit(c, i, gr) * 576, p.xr.data() + (gr * v.nch + c) * 576, 2304);
-            v.side[v.unit(c, i, gr)] = p.side[gr * v.nch + c];
-        }
-}
-template <>
-void parse_into<Mp3Huffman>(const Mp3Huffman::BatchView &v, std::size_t i, const Mp3Huffman::Packet &p) {
-    for (size_t gr = 0; gr < v.ngr; ++gr) {
-        for (size_t c = 0; c < v.nch; ++c) {
-            const size_t dst = v.unit(c, i, gr);
-            std::memcpy(v.quant + dst * 576, p.quant.data() + (gr * v.nch + c) * 576, 1152);
-            v.rq[dst] = p.rq[gr * v.nch + c];
-            v.side[dst] = p.side[gr * v.nch + c];
-        }
-        v.stereo[i * v.ngr + gr] = p.stereo[gr];
-    }
-}
-
 template <class Codec>
 typename Codec::Params params();
 template <>
@@ -370,7 +338,9 @@ int run(const Args &a, const char *codec_name, size_t frames_per_packet, size_t 
                 d.avail = [st]() { return st->limit - std::min(st->limit, st->cursor); };
                 d.parse_into = [st, &pool](const typename Codec::BatchView &v, size_t i) -> std::optional<uint64_t> {
                     if (st->cursor >= st->limit) return std::nullopt;
-                    parse_into<Codec>(v, i, pool[(st->cursor + st->salt) % kPool]);
+                    // the "parser" writes the next packet straight into the batcher's slot with the codec's own placement: one copy of the
+                    // parsed packet (pool -> slot) instead of two (pool -> Packet -> slot)
+                    Codec::put(v, i, pool[(st->cursor + st->salt) % kPool]);
                     return st->cursor++;
                 };
                 if (a.via_registry)
