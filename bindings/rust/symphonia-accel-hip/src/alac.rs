@@ -13,7 +13,7 @@ use symphonia_core::errors::{decode_error, unsupported_error, Result};
 use symphonia_core::packet::PacketRef;
 use symphonia_core::support_audio_codec;
 
-use crate::ctx::{check, narrow_words, place_rows, Context, Pinned, Pool, SlotCycle};
+use crate::ctx::{check, narrow_words, pack_rows, place_rows, Context, Pinned, Pool, SlotCycle};
 use crate::decoder::DecoderBatch;
 use crate::ffi;
 use crate::lookahead::{BatchCodec, Lookahead};
@@ -192,6 +192,8 @@ pub struct AlacBatch {
     // the batches submitted with their words as i16 (every word fits: ctx.rs narrow_words) and as i32
     narrow_batches: usize,
     wide_batches: usize,
+    // the rows sent with a width of their own (SYMACCEL_NARROW_INPUT=2: ctx.rs pack_rows) at 2, 3 and 4 bytes a word
+    rows_sent: [usize; 3],
 }
 
 /// Where `publish` finds a packet in its batch, and what is left to do to it.
@@ -317,16 +319,33 @@ impl BatchCodec for AlacBatch {
         }
         // a batch whose every word fits i16 goes up as i16 (the gather of the launch widens it); per batch
         let packed = if self.slots.narrow_input() { narrow_words(batch, |p| p.words.as_slice()) } else { None };
-        let in_fmt = if packed.is_some() { ffi::SYMACCEL_FMT_S16 as i32 } else { 0 };
-        if packed.is_some() {
+        // a width per row: every subframe at the narrowest of 2, 3 or 4 bytes a word that holds it, found while it is packed
+        let rows = if self.slots.input_mode() == 2 { Some(pack_rows(batch, nch, |p| p.words.as_slice())) } else { None };
+        let in_fmt = if rows.is_some() {
+            ffi::SYMACCEL_IN_FMT_ROWS as i32
+        } else if packed.is_some() {
+            ffi::SYMACCEL_FMT_S16 as i32
+        } else {
+            0
+        };
+        if let Some(r) = &rows {
+            for w in 0..3 {
+                self.rows_sent[w] += r.counts[w];
+            }
+        } else if packed.is_some() {
             self.narrow_batches += 1;
         } else {
             self.wide_batches += 1;
         }
         self.slots.submit_io(ffi::SYMACCEL_BATCH_ALAC_PREDICT as i32, 0, k * nch, stride, in_fmt, Self::index_of(batch, stride), |slot| {
-            match &packed {
-                Some(rows) => place_rows(slot.input::<i16>(0), rows, nch, stride, 0, |r| r.as_slice()),
-                None => place_rows(slot.input::<i32>(0), batch, nch, stride, 0, |p| p.words.as_slice()),
+            if let Some(r) = &rows {
+                r.place(slot.input::<u8>(0), stride);
+                slot.input::<u8>(5).copy_from_slice(r.widths.as_slice());
+            } else {
+                match &packed {
+                    Some(rows) => place_rows(slot.input::<i16>(0), rows, nch, stride, 0, |r| r.as_slice()),
+                    None => place_rows(slot.input::<i32>(0), batch, nch, stride, 0, |p| p.words.as_slice()),
+                }
             }
             place_rows(slot.input::<ffi::SymaccelAlacDesc>(1), batch, nch, 1, NO_DESC, |p| p.desc.as_slice());
             place_rows(slot.input::<i32>(2), batch, nch, 32, 0, |p| p.coeffs.as_slice());
@@ -372,6 +391,11 @@ impl HipAlacDecoder {
         self.batch.wide_batches
     }
 
+    /// The rows (subframes) this decoder sent with a width of their own at 2, 3 and 4 bytes a word (SYMACCEL_NARROW_INPUT=2).
+    pub fn rows_sent(&self) -> [usize; 3] {
+        self.batch.rows_sent
+    }
+
     pub fn try_new_with_pool(
         _params: &AudioCodecParameters,
         _opts: &AudioDecoderOptions,
@@ -399,6 +423,7 @@ impl HipAlacDecoder {
                 buf: AudioBuffer::new(AudioSpec::new(rate, channels), max_frames),
                 narrow_batches: 0,
                 wide_batches: 0,
+                rows_sent: [0; 3],
             },
             la: Lookahead::new(max_batch),
         })

@@ -72,9 +72,10 @@ impl Drop for Context {
 pub struct Pool {
     batcher: *mut ffi::SymaccelBatcher,
     ctx: Context, // (declared after `batcher`: Drop destroys the batcher first, then the field drops the context)
-    /// SYMACCEL_NARROW_INPUT, read once when the pool is made: the FLAC / ALAC decoders send a batch whose every word fits `i16` up as
-    /// `i16` (`symaccel_batcher_reserve_io`).  Off unless the variable is set to something other than 0.
-    narrow: bool,
+    /// SYMACCEL_NARROW_INPUT, read once when the pool is made: how the FLAC / ALAC decoders send their words up.  Unset or 0: wide, every
+    /// batch as `i32`.  2: a width per row (`SYMACCEL_IN_FMT_ROWS`), every subframe at the narrowest of 2, 3 or 4 bytes a word that holds
+    /// it.  Anything else (1): a batch whose every word fits `i16` goes up as `i16`, any other wide (`symaccel_batcher_reserve_io`).
+    input_mode: u8,
 }
 
 unsafe impl Send for Pool {}
@@ -107,18 +108,31 @@ impl Pool {
         let mut batcher = ptr::null_mut();
         // SAFETY: valid context, valid out-pointer.
         check(unsafe { ffi::symaccel_batcher_create(ctx.raw(), 0, &mut batcher) }, ctx.raw())?;
-        let narrow = match std::env::var("SYMACCEL_NARROW_INPUT") {
-            Ok(v) => !v.is_empty() && v != "0",
-            Err(_) => false,
+        let input_mode: u8 = match std::env::var("SYMACCEL_NARROW_INPUT") {
+            Ok(v) => {
+                if v == "2" {
+                    2
+                } else if !v.is_empty() && v != "0" {
+                    1
+                } else {
+                    0
+                }
+            }
+            Err(_) => 0,
         };
-        let pool = Arc::new(Pool { batcher, ctx, narrow });
+        let pool = Arc::new(Pool { batcher, ctx, input_mode });
         *slot = Some(pool.clone());
         Ok(pool)
     }
 
-    /// Do the FLAC / ALAC decoders of this pool narrow their batches (SYMACCEL_NARROW_INPUT at its creation)?
+    /// Do the FLAC / ALAC decoders of this pool narrow whole batches (SYMACCEL_NARROW_INPUT=1 at its creation)?
     pub fn narrow_input(&self) -> bool {
-        self.narrow
+        self.input_mode == 1
+    }
+
+    /// SYMACCEL_NARROW_INPUT at the pool's creation: 0 = wide, 1 = whole batches as `i16` when they fit, 2 = a width per row.
+    pub fn input_mode(&self) -> u8 {
+        self.input_mode
     }
 
     pub(crate) fn raw(&self) -> *mut ffi::SymaccelBatcher {
@@ -370,6 +384,14 @@ impl<M> SlotCycle<M> {
         }
     }
 
+    /// The pool's input mode (`Pool::input_mode`).  0 without a pool.
+    pub fn input_mode(&self) -> u8 {
+        match &self.pool {
+            Some(pool) => pool.input_mode(),
+            None => 0,
+        }
+    }
+
     /// `submit` with an input format (`Pool::reserve_io`): `fill` writes plane 0 as `i16` words when `in_fmt` is `SYMACCEL_FMT_S16`.
     pub fn submit_io<F: FnOnce(&mut BatchSlot) -> Result<()>>(&mut self, kind: i32, param: i32, n_chains: usize, units: usize, in_fmt: i32, index: M, fill: F) -> Result<()> {
         let Some(pool) = self.pool.clone() else {
@@ -471,6 +493,47 @@ pub(crate) fn narrow_words<P>(batch: &[P], words: impl Fn(&P) -> &[i32]) -> Opti
         packed.push(dst);
     }
     Some(packed)
+}
+
+/// The rows of a batch for `SYMACCEL_IN_FMT_ROWS`: row `i * nch + c` is channel `c` of packet `i`, packed at the narrowest of 2, 3 or 4
+/// bytes a word that holds every word of it (`symaccel_host_pack_row` decides and packs), its width, and the rows per width.
+pub(crate) struct PackedRows {
+    pub rows: Vec<Vec<u8>>,
+    pub widths: Vec<u8>,
+    pub counts: [usize; 3],
+}
+
+/// No pass over the batch in front and no prefix sum: every row is packed on its own.  A 17-bit warm-up costs its row a third byte a
+/// word, not the batch its narrow transport.
+pub(crate) fn pack_rows<P>(batch: &[P], nch: usize, words: impl Fn(&P) -> &[i32]) -> PackedRows {
+    let mut packed = PackedRows { rows: Vec::with_capacity(batch.len() * nch), widths: Vec::with_capacity(batch.len() * nch), counts: [0; 3] };
+    for p in batch.iter() {
+        let src = words(p);
+        let w = src.len() / nch;
+        for c in 0..nch {
+            let row = &src[c * w..(c + 1) * w];
+            let mut dst = vec![0u8; 4 * w];
+            // SAFETY: `row` holds `w` words, `dst` the 4 * w bytes the widest packing takes; plain host code.
+            let width = unsafe { ffi::symaccel_host_pack_row(row.as_ptr(), dst.as_mut_ptr() as *mut core::ffi::c_void, w) } as usize;
+            dst.truncate(w * width);
+            packed.counts[width - 2] += 1;
+            packed.widths.push(width as u8);
+            packed.rows.push(dst);
+        }
+    }
+    packed
+}
+
+impl PackedRows {
+    /// Into plane 0 of a slot whose rows are `pitch` words apart: row `r` starts where it starts in the native plane, at byte
+    /// `r * pitch * 4`; zero words at the row's width behind a shorter one.  The bytes of the row's region behind that are not read.
+    pub fn place(&self, dst: &mut [u8], pitch: usize) {
+        for (r, row) in self.rows.iter().enumerate() {
+            let at = r * pitch * 4;
+            dst[at..at + row.len()].copy_from_slice(row);
+            dst[at + row.len()..at + pitch * self.widths[r] as usize].fill(0);
+        }
+    }
 }
 
 /// Page-locked host memory (symaccel_host_alloc): what the staged host entry points need to overlap H2D, kernels and D2H.

@@ -52,7 +52,7 @@
 extern "C" {
 #endif
 
-#define SYMACCEL_ABI_VERSION 8 /* 2: *_pp_device entry points, per-block status arrays, lookahead staging; 3: multi-GPU, probe; 4: mp3_decode_*device, vorbis floor_y; 5: aac_decode_pipelined, aac_joint_stereo_list, vorbis_decode; 6: batcher; 7: batch kinds for Vorbis from posts, FLAC and ALAC (symaccel_batch_slot has six input planes), lanes, per-ticket status; 8: *_strided_device (padded row pitch for the FLAC / ALAC planes), symaccel_row_stride; additions within 8: symaccel_md5_*, symaccel_flac_md5(_device) (STREAMINFO MD5), SYMACCEL_FMT_*, symaccel_sample_bytes, symaccel_pcm_convert(_device), symaccel_batcher_reserve_fmt / _submit_fmt, symaccel_adpcm_*, symaccel_mpa12_* (Layer I / II from sample codes), symaccel_batcher_reserve_io / _submit_io and symaccel_host_narrow_s16 (FLAC / ALAC input as int16_t) */
+#define SYMACCEL_ABI_VERSION 8 /* 2: *_pp_device entry points, per-block status arrays, lookahead staging; 3: multi-GPU, probe; 4: mp3_decode_*device, vorbis floor_y; 5: aac_decode_pipelined, aac_joint_stereo_list, vorbis_decode; 6: batcher; 7: batch kinds for Vorbis from posts, FLAC and ALAC (symaccel_batch_slot has six input planes), lanes, per-ticket status; 8: *_strided_device (padded row pitch for the FLAC / ALAC planes), symaccel_row_stride; additions within 8: symaccel_md5_*, symaccel_flac_md5(_device) (STREAMINFO MD5), SYMACCEL_FMT_*, symaccel_sample_bytes, symaccel_pcm_convert(_device), symaccel_batcher_reserve_fmt / _submit_fmt, symaccel_adpcm_*, symaccel_mpa12_* (Layer I / II from sample codes), symaccel_batcher_reserve_io / _submit_io and symaccel_host_narrow_s16 (FLAC / ALAC input as int16_t), SYMACCEL_IN_FMT_ROWS and symaccel_host_pack_row (a width per row: 16, packed 24 or 32 bit) */
 
 typedef enum symaccel_status {
     SYMACCEL_OK = 0,
@@ -1051,7 +1051,18 @@ int symaccel_batcher_submit_fmt(symaccel_batcher *b, int kind, int param, size_t
  * input_bytes[0] are not read.  submit_io() takes the narrow plane from input[0].  Submissions of either input format share the groups and
  * launches of their (kind, param, units_per_chain), and a group is cut into the chunks it would be cut into if every submission were wide.
  * The library itself never chooses the format.  The decoders above it (C++ codecs::Flac, the Rust shim's FLAC and ALAC decoders) send a
- * batch narrow when every word of it fits and SYMACCEL_NARROW_INPUT=1 was set when their batcher was made; otherwise wide. */
+ * batch narrow when every word of it fits and SYMACCEL_NARROW_INPUT=1 was set when their batcher was made; otherwise wide.
+ * in_fmt SYMACCEL_IN_FMT_ROWS -- the same two kinds, every param form, any out_fmt / channels -- gives every ROW (a chain: one subframe)
+ * a width of its own: row r of plane 0 begins where it begins in the native plane, at byte r * units_per_chain * 4 of slot.input[0], and
+ * its first units_per_chain * w bytes hold its words at w = row_bytes[r] bytes each -- 2: int16_t; 3: little-endian two's-complement 24-bit
+ * words, packed; 4: int32_t.  The bytes of a row's region behind those are not read (the gather kernel reads the slot over the link itself:
+ * what nobody reads costs nothing), every row starts 4-byte aligned, and rows are filled independently, with no prefix sum.
+ * slot.input_bytes[0] stays the native size; slot.input[5] is the width table, uint8_t row_bytes[n_chains] (input_bytes[5] = n_chains),
+ * read by the host when the group is launched and never copied to the device.  A width byte outside {2, 3, 4} fails the ticket alone with
+ * SYMACCEL_ERR_INVALID_ARG, as a bad descriptor does.  submit_io() takes the rows from input[0] (at their native offsets) and the table
+ * from input[5], and copies only the valid bytes of each row.  One 17-bit word then costs its row a third byte a word, not the whole batch
+ * its narrow transport, and a 24-bit stream goes up at 3/4 of its native bytes: SYMACCEL_NARROW_INPUT=2 makes the decoders send rows. */
+#define SYMACCEL_IN_FMT_ROWS 32 /* (not a sample format: outside SYMACCEL_FMT_*) */
 int symaccel_batcher_reserve_io(symaccel_batcher *b, int kind, int param, size_t n_chains, size_t units_per_chain, int in_fmt, int out_fmt,
                                 int channels, symaccel_batch_slot *slot, uint64_t *ticket);
 int symaccel_batcher_submit_io(symaccel_batcher *b, int kind, int param, size_t n_chains, size_t units_per_chain, const void **input,
@@ -1059,6 +1070,10 @@ int symaccel_batcher_submit_io(symaccel_batcher *b, int kind, int param, size_t 
 /* Plain host code for the front ends that decide and pack in one pass: writes (int16_t)src[i] to dst[i] for all n words and returns 1 if
  * every word fits int16_t, 0 if some word does not (dst is then unspecified).  n == 0: 1. */
 int symaccel_host_narrow_s16(const int32_t *src, int16_t *dst, size_t n);
+/* Plain host code for the front ends of SYMACCEL_IN_FMT_ROWS: finds the narrowest of 2, 3 or 4 bytes a word that holds every one of the n
+ * words of a row, writes the row to dst at that width (n * width bytes; dst does not overlap src) and returns the width -- the row's byte
+ * of the width table.  n == 0: 2. */
+int symaccel_host_pack_row(const int32_t *src, void *dst, size_t n);
 /* submit() with the argument lists of the entry points the kinds stand for (symaccel_aac_synth, symaccel_mp3_synth,
  * symaccel_mp3_decode_pipelined for one stream: n_chains 1, or 2 = one channel pair with st_desc[granule]; st_desc may be NULL for 1) */
 int symaccel_batcher_submit_aac_synth(symaccel_batcher *b, const float *coeffs, const uint8_t *side, float *delay_io, float *pcm,

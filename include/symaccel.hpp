@@ -133,7 +133,10 @@ class Batcher {
 public:
     explicit Batcher(Context &ctx, std::size_t flush_bytes = 0) : ctx_(ctx) {
         check(symaccel_batcher_create(ctx.raw(), flush_bytes, &b_), ctx.raw());
-        if (const char *e = std::getenv("SYMACCEL_NARROW_INPUT")) narrow_input_ = std::atoi(e) != 0;  // (read once, like the library's own batcher knobs)
+        if (const char *e = std::getenv("SYMACCEL_NARROW_INPUT")) {  // (read once, like the library's own batcher knobs)
+            const int v = std::atoi(e);
+            input_mode_ = v == 2 ? InputMode::Rows : v != 0 ? InputMode::NarrowBatches : InputMode::Wide;
+        }
     }
     ~Batcher() {
         if (b_) symaccel_batcher_destroy(b_);
@@ -150,15 +153,21 @@ public:
         return s;
     }
     // symaccel_batcher_reserve_io: a slot whose plane 0 takes int16_t words (in_fmt SYMACCEL_FMT_S16; FLAC_RESTORE / ALAC_PREDICT), widened in
-    // the gather of the launch; in_fmt 0 = the native planes.  out_fmt / channels as symaccel_batcher_reserve_fmt takes them (0 = native).
+    // the gather of the launch; in_fmt SYMACCEL_IN_FMT_ROWS: every row of plane 0 at its native offset at 2, 3 or 4 bytes a word, the widths in
+    // slot->input[5]; in_fmt 0 = the native planes.  out_fmt / channels as symaccel_batcher_reserve_fmt takes them (0 = native).
     void reserve_io(int kind, int param, std::size_t n_chains, std::size_t units_per_chain, int in_fmt, int out_fmt, int channels, symaccel_batch_slot *slot,
                     std::uint64_t *ticket) {
         check(symaccel_batcher_reserve_io(b_, kind, param, n_chains, units_per_chain, in_fmt, out_fmt, channels, slot, ticket), ctx_.raw());
     }
-    // Whether the FLAC decoders on this batcher send a batch whose every word fits int16_t as int16_t: SYMACCEL_NARROW_INPUT=1 when the
-    // batcher is made, or set_narrow_input(true); otherwise every batch goes up wide, as it always did.  Read by a decoder when it attaches.
-    bool narrow_input() const { return narrow_input_; }
-    void set_narrow_input(bool on) { narrow_input_ = on; }
+    // How the FLAC decoders on this batcher send plane 0 up; read by a decoder when it attaches.  SYMACCEL_NARROW_INPUT when the batcher is
+    // made, or the setters: unset or 0 = Wide, every batch as int32_t, as it always was; 1 = NarrowBatches (set_narrow_input(true)), a batch
+    // whose every word fits int16_t goes as int16_t and any other wide; 2 = Rows, every row (subframe) at the narrowest of 2, 3 or 4 bytes a
+    // word that holds it (SYMACCEL_IN_FMT_ROWS), decided while the slot is filled, with no pass over the batch in front.
+    enum class InputMode { Wide = 0, NarrowBatches = 1, Rows = 2 };
+    InputMode input_mode() const { return input_mode_; }
+    void set_input_mode(InputMode m) { input_mode_ = m; }
+    bool narrow_input() const { return input_mode_ == InputMode::NarrowBatches; }
+    void set_narrow_input(bool on) { input_mode_ = on ? InputMode::NarrowBatches : InputMode::Wide; }
     // The process-wide batcher (the Rust shim's Pool::shared(), bindings/rust/symphonia-accel-hip/src/ctx.rs): device 0, the library's
     // default flush size, created on first use and never destroyed (decoders of any thread may hold it until the process ends).  This is
     // what a factory that sees (params, options) alone -- CodecRegistry::make_audio_decoder below, registry.rs:330-341 -- builds through.
@@ -187,7 +196,7 @@ public:
 private:
     Context &ctx_;
     symaccel_batcher *b_ = nullptr;
-    bool narrow_input_ = false;
+    InputMode input_mode_ = InputMode::Wide;
 };
 
 namespace dsp {
@@ -629,13 +638,16 @@ struct CodecBase {
     // slot is reserved: `prepare(batch)`
     template <class B>
     void prepare(const B &) {}
-    // ... and one whose plane 0 may go up as int16_t says so per batch, before the slot is reserved: `input_format(batch)` = 0 or
-    // SYMACCEL_FMT_S16 (symaccel_batcher_reserve_io); its fill_slot() then writes plane 0 in that format.  narrow_batches() /
-    // wide_batches(): the batches it submitted either way
+    // ... and one whose plane 0 may go up narrower says so per batch, before the slot is reserved: `input_format(batch)` = 0,
+    // SYMACCEL_FMT_S16 or SYMACCEL_IN_FMT_ROWS (symaccel_batcher_reserve_io); its fill_slot() then writes plane 0 in that format.
+    // narrow_batches() / wide_batches(): the batches it submitted as int16_t / int32_t; rows_sent(): the rows it sent with a width of their
+    // own, at 2, 3 and 4 bytes a word; plane0_bytes(): the bytes of plane 0 it handed to the batcher in all
     template <class B>
     int input_format(const B &) { return 0; }
     std::size_t narrow_batches() const { return 0; }
     std::size_t wide_batches() const { return 0; }
+    std::array<std::size_t, 3> rows_sent() const { return {0, 0, 0}; }
+    std::size_t plane0_bytes() const { return 0; }
     // A codec with no host parse stage (ADPCM) finds a packet's own errors -- a rejected preamble, a packet shorter than its blocks -- when
     // the batch is assembled.  It keeps them per packet (`packet_error(i)`), the packet runs as silence, and decode() throws the error when
     // THAT packet's turn comes: a packet fails alone (codecs/audio.rs:273-278), its neighbours in the look-ahead batch keep their PCM.
@@ -810,6 +822,9 @@ public:
     // the batches this decoder submitted with plane 0 as int16_t / as int32_t (a codec with input_format(): Flac; 0 for the others)
     std::size_t narrow_batches() const { return codec_.narrow_batches(); }
     std::size_t wide_batches() const { return codec_.wide_batches(); }
+    // ... the rows it sent with a width of their own (Batcher::InputMode::Rows) at 2, 3 and 4 bytes a word, and the bytes of plane 0 in all
+    std::array<std::size_t, 3> rows_sent() const { return codec_.rows_sent(); }
+    std::size_t plane0_bytes() const { return codec_.plane0_bytes(); }
 
 private:
     std::vector<Packet> gather(const Packet *first) {
@@ -1718,11 +1733,14 @@ struct Flac : CodecBase {
     // leaves the pair decorrelated and left-justified) for two channels, 0x200 otherwise.
     static constexpr int kBatchKind = SYMACCEL_BATCH_FLAC_RESTORE;
     static constexpr bool kVerifies = true;
-    void attach(Batcher &b) { narrow_ok_ = b.narrow_input(); }
+    void attach(Batcher &b) { narrow_ok_ = b.narrow_input(), rows_ok_ = b.input_mode() == Batcher::InputMode::Rows; }
     // The input format of a batch (LookaheadDecoder asks before it reserves: the format belongs to the reservation): int16_t when EVERY
     // warm-up sample and residual of the batch fits -- the 16-bit streams, but for a side channel's 17-bit warm-up here and there --, else
-    // the native words exactly as before.  Per batch; nothing else about the decoder depends on it.
+    // the native words exactly as before.  Per batch; nothing else about the decoder depends on it.  Batcher::InputMode::Rows: a width per
+    // row, which fill_slot() finds as it packs -- nothing to look at here.
     int input_format(const std::vector<Packet> &batch) {
+        narrow_next_ = false;
+        if ((rows_next_ = rows_ok_)) return SYMACCEL_IN_FMT_ROWS;
         std::uint32_t miss = 0;
         if (narrow_ok_)
             for (const Packet &p : batch)
@@ -1733,6 +1751,8 @@ struct Flac : CodecBase {
     }
     std::size_t narrow_batches() const { return narrow_batches_; }
     std::size_t wide_batches() const { return wide_batches_; }
+    std::array<std::size_t, 3> rows_sent() const { return rows_sent_; }
+    std::size_t plane0_bytes() const { return plane0_bytes_; }
     int batch_param() const {
         if (hashing()) return (nch_ == 2 ? (int)(0x300u | shift_) : 0x200) | (int)((nch_ - 1) << 12);
         return nch_ == 2 ? (int)(0x100u | shift_) : 0;
@@ -1750,7 +1770,16 @@ struct Flac : CodecBase {
             check_shape(p, max_bs_);
             next_lens_[i] = p.blocksize;
             for (std::size_t c = 0; c < nch_; ++c) {
-                if (narrow_next_) {  // (input_format() found that every word fits: packed straight into the slot)
+                if (rows_next_) {  // the row at the narrowest width that holds it, at its native offset; zero is zero at any width
+                    const std::size_t r = i * nch_ + c;
+                    std::uint8_t *row = static_cast<std::uint8_t *>(slot.input[0]) + r * max_bs_ * 4;
+                    const int w = symaccel_host_pack_row(p.words.data() + c * p.blocksize, row, p.blocksize);
+                    if (w < 2 || w > 4) throw std::logic_error("Flac: symaccel_host_pack_row");
+                    std::fill(row + p.blocksize * (std::size_t)w, row + max_bs_ * (std::size_t)w, (std::uint8_t)0);
+                    static_cast<std::uint8_t *>(slot.input[5])[r] = (std::uint8_t)w;
+                    ++rows_sent_[(std::size_t)w - 2];
+                    plane0_bytes_ += max_bs_ * (std::size_t)w;
+                } else if (narrow_next_) {  // (input_format() found that every word fits: packed straight into the slot)
                     std::int16_t *row = static_cast<std::int16_t *>(slot.input[0]) + (i * nch_ + c) * max_bs_;
                     if (!symaccel_host_narrow_s16(p.words.data() + c * p.blocksize, row, p.blocksize)) throw std::logic_error("Flac: a narrow batch with a wide word");
                     std::fill(row + p.blocksize, row + max_bs_, (std::int16_t)0);
@@ -1765,6 +1794,7 @@ struct Flac : CodecBase {
             if (hashing()) static_cast<symaccel_flac_md5_frame *>(slot.input[3])[i] = md5_frame(p);
             else if (nch_ == 2) static_cast<std::uint8_t *>(slot.input[3])[i] = p.pair_mode;
         }
+        if (!rows_next_) plane0_bytes_ += k * nch_ * max_bs_ * (narrow_next_ ? 2 : 4);
         if (hashing()) static_cast<symaccel_md5_state *>(slot.state[0])[0] = chain_end_;
     }
     void take_state(const symaccel_batch_slot &slot) {
@@ -1855,6 +1885,9 @@ private:
     bool verify_ = false, replaying_ = false;
     bool narrow_ok_ = false, narrow_next_ = false;  // the batcher's setting (attach); the format of the batch being submitted
     std::size_t narrow_batches_ = 0, wide_batches_ = 0;
+    bool rows_ok_ = false, rows_next_ = false;  // Batcher::InputMode::Rows (attach); the batch being submitted carries a width per row
+    std::array<std::size_t, 3> rows_sent_{{0, 0, 0}};
+    std::size_t plane0_bytes_ = 0;
     symaccel_md5_state published_{}, chain_end_{};
     std::vector<symaccel_md5_state> cps_;  // the state after every packet of the current batch
     std::vector<symaccel_flac_md5_frame> frames_;

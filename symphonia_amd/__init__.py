@@ -12,7 +12,7 @@ from .backend import (PinnedBuffer, Batcher, BatchSlot, BATCH_AAC_SYNTH, BATCH_M
                       aac_side, alac_desc, flac_desc, mp3_side, FLAC_FIXED, FLAC_LPC, FLAC_VERBATIM,
                       MD5_STATE_DTYPE, FLAC_MD5_FRAME_DTYPE, FLAC_MD5_JOB_DTYPE, flac_bytes_per_sample, md5_init, md5_update, md5_digest, flac_md5_frames, flac_md5,
                       flac_md5_device, flac_md5_finish_device,
-                      FMT_U8, FMT_S8, FMT_U16, FMT_S16, FMT_U24, FMT_S24, FMT_U32, FMT_S32, FMT_F32, SAMPLE_FORMATS, sample_format, sample_bytes, pcm_convert,
+                      FMT_U8, FMT_S8, FMT_U16, FMT_S16, FMT_U24, FMT_S24, FMT_U32, FMT_S32, FMT_F32, SAMPLE_FORMATS, sample_format, sample_bytes, pcm_convert, IN_FMT_ROWS, input_format, host_pack_row,
                       pcm_convert_device,
                       ADPCM_MS, ADPCM_IMA_WAV, ADPCM_IMA_QT, ADPCM_CODECS, adpcm_codec, adpcm_block_bytes, adpcm_decode, adpcm_decode_device,
                       MPA_LAYER1, MPA_LAYER2, Mpa12Decode,

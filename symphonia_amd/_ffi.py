@@ -27,6 +27,7 @@ TABLE_MP3_POW43, TABLE_MP3_POW2AB, TABLE_MPA12 = 8, 9, 10
 
 # SYMACCEL_FMT_*: the sample formats PCM can be delivered in (symaccel_pcm_convert)
 FMT_U8, FMT_S8, FMT_U16, FMT_S16, FMT_U24, FMT_S24, FMT_U32, FMT_S32, FMT_F32 = range(1, 10)
+IN_FMT_ROWS = 32  # SYMACCEL_IN_FMT_ROWS: an INPUT format of symaccel_batcher_reserve_io, a width per row (not a sample format)
 
 # SYMACCEL_ADPCM_*: the codecs of symaccel_adpcm_decode
 ADPCM_MS, ADPCM_IMA_WAV, ADPCM_IMA_QT = 1, 2, 3
@@ -71,7 +72,7 @@ ABI_SYMBOLS = [
     "symaccel_flac_md5_finish_device", "symaccel_batcher_submit_flac_verify",
     "symaccel_sample_bytes", "symaccel_pcm_convert_device", "symaccel_pcm_convert",
     "symaccel_batcher_reserve_fmt", "symaccel_batcher_submit_fmt",
-    "symaccel_batcher_reserve_io", "symaccel_batcher_submit_io", "symaccel_host_narrow_s16",
+    "symaccel_batcher_reserve_io", "symaccel_batcher_submit_io", "symaccel_host_narrow_s16", "symaccel_host_pack_row",
     "symaccel_adpcm_block_bytes", "symaccel_adpcm_decode_device", "symaccel_adpcm_decode",
     "symaccel_batcher_submit_adpcm_decode",
     "symaccel_pcm_coded_bytes", "symaccel_pcm_native_bytes", "symaccel_pcm_decode_device", "symaccel_pcm_decode",
@@ -166,6 +167,7 @@ class Library:
         d.symaccel_batcher_reserve_io.argtypes = [_vp, _i, _i, _sz, _sz, _i, _i, _i, _vp, C.POINTER(C.c_uint64)]
         d.symaccel_batcher_submit_io.argtypes = [_vp, _i, _i, _sz, _sz, _vp, _vp, _vp, _i, _i, _i, C.POINTER(C.c_uint64)]
         d.symaccel_host_narrow_s16.argtypes = [_vp, _vp, _sz]
+        d.symaccel_host_pack_row.argtypes = [_vp, _vp, _sz]
         d.symaccel_batcher_collect.argtypes = [_vp, C.c_uint64]
         d.symaccel_batcher_abandon.argtypes = [_vp, C.c_uint64]
         d.symaccel_batcher_submit_aac_synth.argtypes = [_vp, _vp, _vp, _vp, _vp, _sz, _sz, C.POINTER(C.c_uint64)]

@@ -763,6 +763,25 @@ def sample_format(fmt):
     return SAMPLE_FORMATS[fmt.lower()] if isinstance(fmt, str) else int(fmt)
 
 
+IN_FMT_ROWS = _ffi.IN_FMT_ROWS
+
+
+def input_format(fmt):
+    """The in_fmt of symaccel_batcher_reserve_io / _submit_io from a value or a name: "rows" (SYMACCEL_IN_FMT_ROWS, a width per row) or
+    a sample format's."""
+    return IN_FMT_ROWS if isinstance(fmt, str) and fmt.lower() == "rows" else sample_format(fmt)
+
+
+def host_pack_row(src, lib=None):
+    """symaccel_host_pack_row: (width, bytes) -- the narrowest of 2, 3 or 4 bytes a word that holds every word of the int32 row `src`,
+    and the row packed at that width (int16 / little-endian packed 24-bit / int32) as a uint8 array of len(src) * width bytes."""
+    lib = lib if lib is not None else _ffi.default_library()
+    a = np.ascontiguousarray(src, np.int32).ravel()
+    dst = np.empty(4 * len(a), np.uint8)
+    w = int(lib.dll.symaccel_host_pack_row(a.ctypes.data, dst.ctypes.data, len(a)))
+    return w, dst[:w * len(a)]
+
+
 def sample_bytes(fmt, lib=None):
     """symaccel_sample_bytes: bytes per sample of a format (the 24-bit formats are three packed bytes); 0 for an unknown one."""
     lib = lib if lib is not None else _ffi.default_library()
@@ -1110,7 +1129,8 @@ class Batcher:
         filled by collect().  out_format (a FMT_* value or name) / channels: symaccel_batcher_submit_fmt -- `out` then receives
         [n_chains / channels][samples][channels] samples of that format (a byte buffer of the native planes' size always holds it) and
         n_chains / units are taken from inputs[0]'s shape unless given.  in_fmt "s16" (FLAC_RESTORE / ALAC_PREDICT): inputs[0] holds
-        int16 words, widened in the gather (symaccel_batcher_submit_io)."""
+        int16 words, widened in the gather (symaccel_batcher_submit_io); in_fmt "rows": inputs[0] is a byte buffer of the native plane's
+        size with every row packed at its native offset (host_pack_row), inputs[5] the uint8 width table, a byte per row."""
         shaped = out if not out_format else inputs[0]
         n_chains, units = int(shaped.shape[0] if n_chains is None else n_chains), int(shaped.shape[1] if units is None else units)
         ins = (C.c_void_p * 6)(*[a.ctypes.data if a is not None else None for a in list(inputs) + [None] * (6 - len(inputs))])
@@ -1120,7 +1140,7 @@ class Batcher:
         t = C.c_uint64()
         if in_fmt:
             self._check(self.dll.symaccel_batcher_submit_io(self.handle, int(kind), int(param), n_chains, units, ins, sts, out.ctypes.data,
-                                                            sample_format(in_fmt), sample_format(out_format) if out_format else 0, int(channels), C.byref(t)))
+                                                            input_format(in_fmt), sample_format(out_format) if out_format else 0, int(channels), C.byref(t)))
         elif out_format:
             self._check(self.dll.symaccel_batcher_submit_fmt(self.handle, int(kind), int(param), n_chains, units, ins, sts, out.ctypes.data,
                                                              sample_format(out_format), int(channels), C.byref(t)))
@@ -1256,10 +1276,11 @@ class Batcher:
     def reserve(self, kind, param, n_chains, units, out_format=0, channels=0, in_fmt=0):
         """out_format / channels: symaccel_batcher_reserve_fmt -- slot.out then receives interleaved samples of that format, slot.out_bytes
         of them valid (wait() returns the count the launch wrote).  in_fmt "s16" (FLAC_RESTORE / ALAC_PREDICT): slot.input[0] takes int16
-        words, slot.input_bytes[0] of them (symaccel_batcher_reserve_io)"""
+        words, slot.input_bytes[0] of them (symaccel_batcher_reserve_io); in_fmt "rows": every row at its native offset of slot.input[0] at a
+        width of its own (2, 3 or 4 bytes a word), the widths in slot.input[5], a byte per row"""
         slot, t = BatchSlot(), C.c_uint64()
         if in_fmt:
-            self._check(self.dll.symaccel_batcher_reserve_io(self.handle, int(kind), int(param), int(n_chains), int(units), sample_format(in_fmt),
+            self._check(self.dll.symaccel_batcher_reserve_io(self.handle, int(kind), int(param), int(n_chains), int(units), input_format(in_fmt),
                                                              sample_format(out_format) if out_format else 0, int(channels), C.byref(slot), C.byref(t)))
         elif out_format:
             self._check(self.dll.symaccel_batcher_reserve_fmt(self.handle, int(kind), int(param), int(n_chains), int(units), sample_format(out_format),

@@ -5,8 +5,8 @@
 // from page-locked memory too.  A workgroup takes one piece of at most 16 KiB: four 16-byte loads per lane in flight, then the
 // stores -- with a grid of thousands of pieces the link sees enough outstanding reads to run at its rate.
 // Two launches do more than copy: the scatter of a chunk with tickets that want their PCM in a sample format converts and interleaves
-// (batch_scatter_convert_kernel), the gather of a chunk with tickets whose FLAC / ALAC words came as int16_t widens them
-// (batch_gather_widen_kernel); every other chunk is moved by batch_copy_kernel.
+// (batch_scatter_convert_kernel), the gather of a chunk with tickets whose FLAC / ALAC words came as int16_t, or row by row as int16_t
+// or packed 24-bit words, widens them (batch_gather_widen_kernel); every other chunk is moved by batch_copy_kernel.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -229,11 +229,72 @@ __device__ __forceinline__ void batch_widen_piece(const BatchCopyDesc d, const u
     if (pr) dst[r] = e;
 }
 
-// (plain pieces -- descriptors, coefficients, state, the rows of the tickets that came wide -- as batch_scatter_convert_kernel copies its own)
+// A PACKED-24 piece (kBatchPieceWiden | kBatchPiecePacked24: a row of a ticket with a width per row, SYMACCEL_IN_FMT_ROWS, sent at 3 bytes a
+// word): `src` = little-endian two's-complement 24-bit words, packed, starting 4-byte aligned; `dst` and `bytes` as above (4096 words are
+// 12 288 bytes of source).  16 words are 48 bytes, three 16-byte units in and four out, and the source is cut where a 16-byte boundary is a
+// word boundary too: a start at 4, 8 or 12 modulo 16 is 4, 8 or 12 words (12, 24, 36 bytes) short of one -- the ragged head --, the body is
+// at most 256 groups of 16 words, one per lane, the tail at most 15 words.  Head and tail go byte by byte on lanes 0..11 and 12..26.
+// The body crosses the link in the plain copy's pattern -- lane to lane 16 bytes apart, three loads a lane, all issued before anything
+// else -- and is dealt out through LDS (12 KiB), so that no load instruction of a wavefront touches a 64-byte line of page-locked memory
+// for 16 bytes of it (a lane that loads its own 48 bytes straight from the slot does, in all three loads).  Measured, the two forms run
+// the same: 24-bit rows 8 to 10 % BELOW the wide transport at 3/4 of its bytes either way (profiles/flac_row_input*.txt) --
+// what packed rows lose is not in how the source is read.  Nothing outside [src, src + 3 * bytes / 4) is read, nothing outside
+// [dst, dst + bytes) written.
+// (four words out of three dwords: bytes 0-2 | 3-5 | 6-8 | 9-11, each shifted to the top and brought down with its sign)
+__device__ __forceinline__ void widen24_store(int32_t *out, const unsigned x, const unsigned y, const unsigned z, const bool aligned) {
+    const int w0 = (int)(x << 8) >> 8, w1 = (int)(((x >> 24) | (y << 8)) << 8) >> 8;
+    const int w2 = (int)(((y >> 16) | (z << 16)) << 8) >> 8, w3 = (int)z >> 8;
+    if (aligned) *reinterpret_cast<widen_v4i *>(out) = widen_v4i{w0, w1, w2, w3};
+    else out[0] = w0, out[1] = w1, out[2] = w2, out[3] = w3;
+}
+
+constexpr unsigned kWiden24Units = 768;  // 16-byte units of a piece's body at most: 256 groups of three
+
+// (every work-item of the workgroup calls it with the same piece: two barriers inside)
+__device__ __forceinline__ void batch_widen24_piece(const BatchCopyDesc d, const unsigned tid, uint4 *image) {
+    const uint8_t *src = static_cast<const uint8_t *>(d.src);
+    int32_t *dst = static_cast<int32_t *>(d.dst);
+    const unsigned n = d.bytes / 4u;  // words, <= 4096
+    const unsigned to_boundary = (unsigned)(reinterpret_cast<uintptr_t>(src) & 15u);  // in WORDS: (s + 3 s) % 16 == 0 for s = 0, 4, 8, 12
+    const unsigned head = to_boundary < n ? to_boundary : n;
+    const unsigned ng = (n - head) / 16u, tail0 = head + 16u * ng;  // ng <= 256
+    const unsigned nu = 3u * ng;                                    // <= kWiden24Units
+    const uint4 *body = reinterpret_cast<const uint4 *>(src + 3u * head);
+    int32_t *out = dst + head;
+    const bool aligned = (reinterpret_cast<uintptr_t>(out) & 15u) == 0;
+    const bool p0 = tid < nu, p1 = tid + 256u < nu, p2 = tid + 512u < nu;
+    // the ragged ends: lanes 0..11 take the head's words, lanes 12..26 the tail's
+    const unsigned r = tid < 12u ? tid : tail0 + (tid - 12u);
+    const bool pr = tid < 12u ? tid < head : (tid < 27u && r < n);
+    uint4 v0 = {}, v1 = {}, v2 = {};
+    unsigned e0 = 0, e1 = 0, e2 = 0;
+    if (p0) v0 = body[tid];
+    if (p1) v1 = body[tid + 256u];
+    if (p2) v2 = body[tid + 512u];
+    if (pr) e0 = src[3u * r], e1 = src[3u * r + 1u], e2 = src[3u * r + 2u];
+    if (p0) image[tid] = v0;
+    if (p1) image[tid + 256u] = v1;
+    if (p2) image[tid + 512u] = v2;
+    __syncthreads();
+    if (tid < ng) {
+        const uint4 a = image[3u * tid], b = image[3u * tid + 1u], c = image[3u * tid + 2u];
+        int32_t *o = out + 16u * tid;
+        widen24_store(o, a.x, a.y, a.z, aligned);
+        widen24_store(o + 4, a.w, b.x, b.y, aligned);
+        widen24_store(o + 8, b.z, b.w, c.x, aligned);
+        widen24_store(o + 12, c.y, c.z, c.w, aligned);
+    }
+    if (pr) dst[r] = (int)((e0 | (e1 << 8) | (e2 << 16)) << 8) >> 8;
+    __syncthreads();  // (the image is the next packed piece's)
+}
+
+// (plain pieces -- descriptors, coefficients, state, the rows that came at 4 bytes a word -- as batch_scatter_convert_kernel copies its own)
 __global__ __launch_bounds__(256) void batch_gather_widen_kernel(const BatchCopyDesc *__restrict__ descs, unsigned n_pieces) {
+    __shared__ uint4 image[kWiden24Units];
     for (unsigned piece = blockIdx.x; piece < n_pieces; piece += gridDim.x) {
         const BatchCopyDesc d = descs[piece];
-        if (d.pad & kBatchPieceWiden) batch_widen_piece(d, threadIdx.x);
+        if (d.pad & kBatchPiecePacked24) batch_widen24_piece(d, threadIdx.x, image);
+        else if (d.pad & kBatchPieceWiden) batch_widen_piece(d, threadIdx.x);
         else batch_copy_piece_beside_tiles(d, threadIdx.x);
     }
 }

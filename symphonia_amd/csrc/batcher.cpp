@@ -250,7 +250,8 @@ struct Ticket {
     uint32_t channels = 0;
     size_t out_valid = 0;
     // the input format (symaccel_batcher_reserve_io): 0 = the native planes, SYMACCEL_FMT_S16 = plane 0 of the slot holds int16_t words
-    // -- the first half of the region the native plane (and the result, in place) has
+    // -- the first half of the region the native plane (and the result, in place) has; SYMACCEL_IN_FMT_ROWS = every row of plane 0 at
+    // its native offset, at a width of its own: the width table (slot.input[5], a byte per row) lies behind the shape's planes in the slot
     int in_fmt = 0;
 };
 
@@ -453,7 +454,17 @@ inline bool vorbis_kind(int kind) { return kind == SYMACCEL_BATCH_VORBIS_SYNTH |
 
 // ---- what a FLAC / ALAC / ADPCM submission's descriptors say, judged alone (its neighbours in the launch are not failed for it; the
 // kinds that have lists judge theirs in batcher_lists.h); then the steps of a launch (launch_group_inner) in their order
+// a ticket with a width per row (SYMACCEL_IN_FMT_ROWS): every byte of its width table is 2, 3 or 4
+bool row_widths_ok(const TicketView &v) {
+    if (v.in_fmt != SYMACCEL_IN_FMT_ROWS) return true;
+    const uint8_t *w = v.row_bytes();
+    for (size_t c = 0; c < v.n_chains; ++c)
+        if (w[c] < 2 || w[c] > 4) return false;
+    return true;
+}
+
 int check_flac(size_t units, int param, const TicketView &v) {
+    if (!row_widths_ok(v)) return SYMACCEL_ERR_INVALID_ARG;
     const FlacVerifyParam vp = flac_verify_param(param);
     if (vp.verify) {  // the frame records, as flac_md5_kernel judges a job -- and every frame names its width
         const symaccel_flac_md5_frame *fr = v.in<const symaccel_flac_md5_frame>(3);
@@ -476,6 +487,7 @@ int check_flac(size_t units, int param, const TicketView &v) {
 }
 
 int check_alac(int param, const TicketView &v) {
+    if (!row_widths_ok(v)) return SYMACCEL_ERR_INVALID_ARG;
     const symaccel_alac_desc *d = v.in<const symaccel_alac_desc>(1);
     for (size_t c = 0; c < v.n_chains; ++c) {
         if (d[c].mode > 0 && d[c].mode < 15) return SYMACCEL_ERR_DECODE;  // lib.rs:167-169, "alac: invalid mode" (symaccel_alac_block_status_device)
@@ -590,6 +602,8 @@ size_t piece_bound(const Group *g) {
     bound += g->tickets + 8;                                // the unit list's pieces, one per chunk at most
     if (g->kind == SYMACCEL_BATCH_FLAC_RESTORE && flac_verify_param(g->param).verify) bound += 2 * g->tickets + 8;  // the job table's, likewise
     if (g->row_pitch) bound += 2 * g->chains;               // rows go one by one, in and out, each rounded up
+    for (const TicketView &v : g->views)
+        if (v.in_fmt == SYMACCEL_IN_FMT_ROWS) bound += v.n_chains;  // ... and the rows of a ticket with a width per row go in one by one always
     if (vorbis_kind(g->kind)) bound += 2 * g->chains;       // spectra and PCM go chain by chain, each rounded up
     if (g->kind == SYMACCEL_BATCH_AAC_DECODE) bound += 3 * g->tickets + 8;  // pair list, filters, TNS pair frames: one piece list each per chunk
     if (g->kind == SYMACCEL_BATCH_VORBIS_DECODE) {          // its six lists: cut once per chunk, each cut rounded up
@@ -710,6 +724,22 @@ void gather_narrow(const Group *g, const TicketView &t, Pieces &pw) {
     for (size_t c = 0; c < t.n_chains; ++c) pw.widen(src + c * (row / 2), g->d_in[0] + ((size_t)t.first_chain + c) * g->row_pitch, row);
 }
 
+// FLAC / ALAC, a submission with a width per row (SYMACCEL_IN_FMT_ROWS): row by row always, every row from its native offset in the slot --
+// a widening piece list at 2 or 3 bytes a word, plain pieces at 4 (and for a width that check_flac / check_alac refused: the ticket has
+// failed, and the row's region is the native row's, so nothing outside the slot is read).  True if a widening piece was written.
+bool gather_row_widths(const Group *g, const TicketView &t, Pieces &pw) {
+    const size_t row = g->ps.in[0], pitch = g->row_pitch ? g->row_pitch : row;
+    const uint8_t *w = t.row_bytes();
+    bool widening = false;
+    for (size_t c = 0; c < t.n_chains; ++c) {
+        const char *src = t.slot + t.lay.in[0] + c * row;
+        char *dst = g->d_in[0] + ((size_t)t.first_chain + c) * pitch;
+        if (w[c] == 2 || w[c] == 3) pw.widen(src, dst, row, w[c]), widening = true;
+        else pw.add(src, dst, row);
+    }
+    return widening;
+}
+
 // gather: the submissions' planes into the chain-major device arrays, and the chunk's lists; true if the list holds widening pieces
 bool build_gather(Group *g, const Chunk &ch, Pieces &pw) {
     bool widening = false;
@@ -719,7 +749,8 @@ bool build_gather(Group *g, const Chunk &ch, Pieces &pw) {
         const TicketView &t = g->views[ti];
         for (int i = 0; i < ps.n_in; ++i) {
             if (ps.in_host_only[i]) continue;
-            if (i == 0 && t.in_fmt) gather_narrow(g, t, pw), widening = true;
+            if (i == 0 && t.in_fmt == SYMACCEL_IN_FMT_ROWS) widening |= gather_row_widths(g, t, pw);
+            else if (i == 0 && t.in_fmt) gather_narrow(g, t, pw), widening = true;
             else if (i == 0 && vorbis_kind(g->kind)) gather_vorbis_spectra(g, t, pw);
             else if (i == 0 && g->row_pitch) gather_rows(g, t, pw);
             else pw.bulk(t.slot + t.lay.in[i], g->d_in[i] + (ps.in_per_ticket[i] ? ti : (size_t)t.first_chain / ps.in_div[i]) * ps.in[i], t.lay.in_bytes[i]);
@@ -1080,7 +1111,11 @@ void fill_slot(const Group *g, const Ticket *t, symaccel_batch_slot *slot) {
         slot->input[i] = t->slot + l.in[i];
         slot->input_bytes[i] = l.in_bytes[i];
     }
-    if (t->in_fmt) slot->input_bytes[0] = l.in_bytes[0] / 2;  // (int16_t words: the front half of the native plane's region)
+    if (t->in_fmt == SYMACCEL_FMT_S16) slot->input_bytes[0] = l.in_bytes[0] / 2;  // (int16_t words: the front half of the native plane's region)
+    if (t->in_fmt == SYMACCEL_IN_FMT_ROWS) {  // (rows at their native offsets: the region as it is; the width table behind the shape's planes)
+        slot->input[5] = t->slot + l.bytes;
+        slot->input_bytes[5] = t->n_chains;
+    }
     for (int i = 0; i < g->ps.n_state; ++i) {
         slot->state[i] = t->slot + l.state[i];
         slot->state_bytes[i] = l.state_bytes[i];
@@ -1201,7 +1236,7 @@ int symaccel_batcher_reserve_fmt(symaccel_batcher *b, int kind, int param, size_
 int symaccel_batcher_reserve_io(symaccel_batcher *b, int kind, int param, size_t n_chains, size_t units_per_chain, int in_fmt, int out_fmt,
                                 int channels, symaccel_batch_slot *slot, uint64_t *ticket) {
     // (the widening happens in the gather, before any kernel of the kind sees the plane: every param form of the two kinds takes it)
-    if (in_fmt != 0 && (in_fmt != SYMACCEL_FMT_S16 || !serial_kind(kind))) return SYMACCEL_ERR_INVALID_ARG;
+    if (in_fmt != 0 && ((in_fmt != SYMACCEL_FMT_S16 && in_fmt != SYMACCEL_IN_FMT_ROWS) || !serial_kind(kind))) return SYMACCEL_ERR_INVALID_ARG;
     if (!b || !slot || !ticket || n_chains == 0 || n_chains > 0x7fffffffu) return SYMACCEL_ERR_INVALID_ARG;
     // (a PCM packet of 0 frames is a packet like any other -- lib.rs:320: floor(len / frame bytes) -- with empty planes: it takes a ticket,
     // rides in the group of its shape and comes back with 0 bytes)
@@ -1233,7 +1268,8 @@ int symaccel_batcher_reserve_io(symaccel_batcher *b, int kind, int param, size_t
     if (kind == SYMACCEL_BATCH_AAC_DECODE && param != -1 && (param < 0 || (size_t)param >= b->bands.size())) return SYMACCEL_ERR_INVALID_ARG;  // (symaccel_batcher_aac_bands first; -1: no pairs, no table)
     // the slot first: page-locking a new slab drops the mutex, and the group must be chosen in one piece with the reservation
     const SlotLayout lay = slot_layout(ps, n_chains);
-    const size_t cls = slot_class(lay.bytes);
+    // (a ticket with a width per row: its width table behind the planes, slot.input[5] -- fill_slot, TicketView::row_bytes)
+    const size_t cls = slot_class(lay.bytes + (in_fmt == SYMACCEL_IN_FMT_ROWS ? round256(n_chains) : 0));
     char *mem = nullptr;
     SYM_TRY(slot_alloc(b, lock, cls, &mem));
     Group *g = open_group(b, kind, param, units_per_chain, ps, n_chains);
@@ -1438,10 +1474,19 @@ int symaccel_batcher_submit_io(symaccel_batcher *b, int kind, int param, size_t 
         if (!in[i] && !(kind == SYMACCEL_BATCH_MP3_DECODE && i == 3 && n_chains == 1)) return SYMACCEL_ERR_INVALID_ARG;
     for (int i = 0; i < ps.n_state; ++i)
         if (!state_io[i]) return SYMACCEL_ERR_INVALID_ARG;
+    const bool rows = in_fmt == SYMACCEL_IN_FMT_ROWS;
+    if (rows && !in[5]) return SYMACCEL_ERR_INVALID_ARG;  // (the width table)
     symaccel_batch_slot slot;
     uint64_t id = 0;
     SYM_TRY(symaccel_batcher_reserve_io(b, kind, param, n_chains, units_per_chain, in_fmt, out_fmt, channels, &slot, &id));
-    for (int i = 0; i < ps.n_in; ++i) {
+    if (rows) {  // the width table, and of every row the bytes its width makes valid (none where the width is none of 2, 3, 4: the ticket fails)
+        const uint8_t *w = static_cast<const uint8_t *>(in[5]);
+        std::memcpy(slot.input[5], w, n_chains);
+        for (size_t c = 0; c < n_chains; ++c)
+            if (w[c] >= 2 && w[c] <= 4)
+                std::memcpy(static_cast<char *>(slot.input[0]) + c * units_per_chain * 4, static_cast<const char *>(in[0]) + c * units_per_chain * 4, units_per_chain * w[c]);
+    }
+    for (int i = rows ? 1 : 0; i < ps.n_in; ++i) {
         if (in[i])
             std::memcpy(slot.input[i], in[i], slot.input_bytes[i]);
         else
@@ -1662,6 +1707,35 @@ int symaccel_host_narrow_s16(const int32_t *src, int16_t *dst, size_t n) {
         miss |= (uint32_t)v ^ (uint32_t)(int32_t)(int16_t)v;
     }
     return miss == 0;
+}
+
+int symaccel_host_pack_row(const int32_t *src, void *dst, size_t n) {
+    if (n && (!src || !dst)) return 0;
+    // the width first: v ^ (v >> 31) is v for v >= 0 and -v - 1 below, so the OR of all of them is below 2^15 (2^23) exactly when every
+    // word fits 16 (24) bits -- no branch in the loop, so it vectorises; then the row at that width
+    uint32_t mag = 0;
+    for (size_t i = 0; i < n; ++i) mag |= (uint32_t)(src[i] ^ (src[i] >> 31));
+    if (mag < 0x8000u) {
+        int16_t *d = static_cast<int16_t *>(dst);
+        for (size_t i = 0; i < n; ++i) d[i] = (int16_t)src[i];
+        return 2;
+    }
+    if (mag < 0x800000u) {
+        uint8_t *d = static_cast<uint8_t *>(dst);
+        size_t i = 0;
+        for (; i + 4 <= n; i += 4) {  // four words, three dwords: a quarter of the stores of the byte-by-byte form
+            const uint32_t a = (uint32_t)src[i], b = (uint32_t)src[i + 1], c = (uint32_t)src[i + 2], e = (uint32_t)src[i + 3];
+            const uint32_t q[3] = {(a & 0xffffffu) | (b << 24), ((b >> 8) & 0xffffu) | (c << 16), ((c >> 16) & 0xffu) | (e << 8)};
+            std::memcpy(d + 3 * i, q, 12);
+        }
+        for (; i < n; ++i) {
+            const uint32_t v = (uint32_t)src[i];
+            d[3 * i] = (uint8_t)v, d[3 * i + 1] = (uint8_t)(v >> 8), d[3 * i + 2] = (uint8_t)(v >> 16);
+        }
+        return 3;
+    }
+    std::memcpy(dst, src, n * 4);
+    return 4;
 }
 
 int symaccel_batcher_collect(symaccel_batcher *b, uint64_t ticket) {

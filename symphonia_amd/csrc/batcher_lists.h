@@ -97,12 +97,15 @@ struct TicketView {
     int out_fmt = 0;
     uint32_t channels = 0;
     size_t out_valid = 0;
-    int in_fmt = 0;                // 0, or SYMACCEL_FMT_S16: plane 0 of the slot holds int16_t words (FLAC_RESTORE / ALAC_PREDICT, symaccel_batcher_reserve_io)
+    int in_fmt = 0;                // 0, or SYMACCEL_FMT_S16: plane 0 of the slot holds int16_t words (FLAC_RESTORE / ALAC_PREDICT, symaccel_batcher_reserve_io);
+                                   // or SYMACCEL_IN_FMT_ROWS: every row at its native offset, at row_bytes()[row] bytes a word
     int fmt_status = SYMACCEL_OK;  // what the output format has to say about the submission (Vorbis: an interleave group whose chains disagree)
     SlotLayout lay;
     const VorbisUsed *used = nullptr;  // the two Vorbis kinds: what the blocks of chain c fill, used[c]
     template <class T> T *in(int i) const { return reinterpret_cast<T *>(slot + lay.in[i]); }
     template <class T> T *state(int i) const { return reinterpret_cast<T *>(slot + lay.state[i]); }
+    // SYMACCEL_IN_FMT_ROWS: the width table (slot.input[5]), behind the planes every ticket of the shape has; read by the host only
+    const uint8_t *row_bytes() const { return reinterpret_cast<const uint8_t *>(slot + lay.bytes); }
 };
 
 // chains [c0, c0 + nc) = submissions [t0, t0 + nt) of a group, and where their planes start on the device
@@ -153,8 +156,11 @@ struct Pieces {
     }
     // int16_t words of a slot -> int32_t words of the device plane: cut by the DESTINATION's bytes, so that a narrow plane is as many
     // pieces as the same plane sent wide (piece_bound() counts it as that); never through a copy engine, which cannot widen
-    void widen(const char *src, char *dst, size_t dst_bytes) {
-        for (size_t o = 0; o < dst_bytes; o += kBatchCopyPiece) piece(src + o / 2, dst + o, std::min(kBatchCopyPiece, dst_bytes - o), kBatchPieceWiden);
+    // (word_bytes 3: packed 24-bit words, a row of a ticket with a width per row; a piece of 4096 words then starts 12 288 bytes behind
+    // the last, so every piece of a row keeps the row's alignment modulo 16)
+    void widen(const char *src, char *dst, size_t dst_bytes, unsigned word_bytes = 2) {
+        for (size_t o = 0; o < dst_bytes; o += kBatchCopyPiece)
+            piece(src + o / 4 * word_bytes, dst + o, std::min(kBatchCopyPiece, dst_bytes - o), batch_piece_widen(word_bytes));
     }
     void bulk(const char *src, char *dst, size_t bytes) {
         if (dma_bytes && bytes >= dma_bytes) dma.push_back({src, dst, bytes});

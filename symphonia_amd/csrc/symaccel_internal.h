@@ -329,6 +329,10 @@ constexpr uint32_t kBatchPieceConvert = 0x80000000u, kBatchPieceFromI32 = 0x10u;
 // int32_t words on the device, bytes = the destination's.  A bit the converting pieces' encoding leaves alone; launch_batch_copy's `widening`
 // says that a gather's list holds such pieces.
 constexpr uint32_t kBatchPieceWiden = 0x40000000u;
+// ... and beside it the width of the source's words where it is not 2: a row of a ticket that came with a width per row
+// (SYMACCEL_IN_FMT_ROWS) at 3 bytes a word -- little-endian two's-complement, packed, src 4-byte aligned.  (A row at 4 bytes is a plain piece.)
+constexpr uint32_t kBatchPiecePacked24 = 0x20000000u;
+constexpr uint32_t batch_piece_widen(unsigned word_bytes) { return kBatchPieceWiden | (word_bytes == 3 ? kBatchPiecePacked24 : 0u); }
 constexpr uint32_t batch_piece_convert(bool from_i32, size_t frames, uint32_t channels, int dst_fmt) {  // the `pad` word of a converting piece
     return kBatchPieceConvert | (from_i32 ? kBatchPieceFromI32 : 0u) | ((uint32_t)frames << 12) | (channels << 8) | (uint32_t)dst_fmt;
 }

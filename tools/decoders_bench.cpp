@@ -46,7 +46,12 @@ struct Args {
     // --bits 16 (FLAC): a pool of 16-bit packets whose every warm-up sample and residual fits int16_t -- what the decoders send up as
     // int16_t (symaccel_batcher_reserve_io).  --narrow 0|1 forces that choice (Batcher::set_narrow_input); without it the batcher's own
     // setting holds (SYMACCEL_NARROW_INPUT).  --narrow 0 is the transport every batch had before there was an input format.
-    size_t bits = 24;
+    // --narrow 2: a width per row (Batcher::InputMode::Rows, SYMACCEL_IN_FMT_ROWS) -- every subframe at the narrowest of 2, 3 or 4 bytes a
+    // word that holds it.  --wide-every N (FLAC): the first warm-up word of the side subframe of every N-th packet of a stream is 40000, a
+    // 17-bit value -- the word that sends a whole batch wide under --narrow 1 and one row to 3 bytes under --narrow 2 (any word is valid
+    // input to the restore).  --warmup-bits B (FLAC): the 32 warm-up words of every subframe of the pool span the whole B-bit range, as a
+    // stream of that depth has them (the pool's own stay within +-1000 at 24 bits, +-12000 at 16).
+    size_t bits = 24, wide_every = 0, warmup_bits = 0;
     int narrow = -1;
     SampleFormat format() const {
         if (out_format == "f32") return SampleFormat::Native;
@@ -60,6 +65,7 @@ struct Args {
 
 constexpr size_t kPool = 32;
 size_t g_flac_bits = 24;  // --bits: what make_pool<Flac> and params<Flac> build
+size_t g_flac_warmup_bits = 0;  // --warmup-bits
 
 template <class Codec>
 std::vector<typename Codec::Packet> make_pool(unsigned seed);
@@ -128,6 +134,17 @@ std::vector<Vorbis::Packet> make_pool<Vorbis>(unsigned seed) {  // BASELINE conf
     return pool;
 }
 
+// --warmup-bits: the 32 warm-up words of every subframe over the whole range of that many bits (a generator of its own: the pools are what
+// they were without the option)
+void flac_warmups(std::vector<Flac::Packet> &pool) {
+    if (!g_flac_warmup_bits) return;
+    std::mt19937 rng(4242);
+    const int64_t top = (int64_t)1 << (g_flac_warmup_bits - 1);
+    for (auto &p : pool)
+        for (size_t i = 0; i < p.words.size(); ++i)
+            if (i % 4096 < 32) p.words[i] = (int32_t)((int64_t)(rng() % (uint64_t)(2 * top)) - top);
+}
+
 template <>
 std::vector<Flac::Packet> make_pool<Flac>(unsigned seed) {  // BASELINE config 5's shape per packet: two subframes of 4096 samples, LPC order 32, 24 bits
     std::mt19937 rng(seed);
@@ -145,6 +162,7 @@ std::vector<Flac::Packet> make_pool<Flac>(unsigned seed) {  // BASELINE config 5
             for (auto &c : p.coeffs) c = (int32_t)(rng() % 121) - 60;
             p.pair_mode = (uint8_t)(rng() % 4);
         }
+        flac_warmups(pool);
         return pool;
     }
     for (auto &p : pool) {
@@ -156,6 +174,7 @@ std::vector<Flac::Packet> make_pool<Flac>(unsigned seed) {  // BASELINE config 5
         for (auto &c : p.coeffs) c = (int32_t)(rng() % 401) - 200;
         p.pair_mode = (uint8_t)(rng() % 4);
     }
+    flac_warmups(pool);
     return pool;
 }
 
@@ -285,8 +304,17 @@ int run(const Args &a, const char *codec_name, size_t frames_per_packet, size_t 
     }
     Context &ctx = a.via_registry ? batcher->context() : *own_ctx;
     if (batcher && a.lanes) check(symaccel_batcher_configure(batcher->raw(), (int)a.lanes, 0), ctx.raw());
-    if (batcher && a.narrow >= 0) batcher->set_narrow_input(a.narrow != 0);  // (before any decoder attaches)
+    if (batcher && a.narrow >= 0) batcher->set_input_mode(a.narrow == 2 ? Batcher::InputMode::Rows : a.narrow ? Batcher::InputMode::NarrowBatches : Batcher::InputMode::Wide);  // (before any decoder attaches)
+    if ((a.wide_every || a.warmup_bits) && !std::is_same<Codec, Flac>::value) throw std::invalid_argument("--wide-every / --warmup-bits: the FLAC pool");
     const std::vector<Packet> pool = make_pool<Codec>(17);
+    // --wide-every: packet `ts` of a stream as the parser hands it over
+    const size_t wide_every = a.wide_every;
+    auto tweak = [wide_every](Packet &p, size_t ts) {
+        if constexpr (std::is_same<Codec, Flac>::value) {
+            if (wide_every && ts % wide_every == 0 && !p.words.empty()) p.words[p.blocksize] = 40000;
+        }
+        (void)p, (void)ts;
+    };
     struct Stream {
         size_t cursor = 0, limit = 0, salt = 0, pos = 0, lead = 0;
         std::unique_ptr<Decoder> dec;
@@ -302,6 +330,7 @@ int run(const Args &a, const char *codec_name, size_t frames_per_packet, size_t 
         if constexpr (std::is_same<Codec, Flac>::value) {
             if (a.format() != SampleFormat::Native) throw std::invalid_argument("--verify: the planes are hashed as they are decoded (no --out-format)");
             if (a.bits != 24) throw std::invalid_argument("--verify: the host-side digests are those of 24-bit samples (no --bits 16)");
+            if (a.wide_every) throw std::invalid_argument("--verify: the digests are those of the pool's packets as they are (no --wide-every)");
             std::vector<size_t> salt(a.streams), count(a.streams);
             for (size_t s = 0; s < a.streams; ++s) salt[s] = s * 7, count[s] = total + lead_of(s);  // (what the two phases below decode of stream s)
             std::vector<Digest> want;
@@ -326,9 +355,10 @@ int run(const Args &a, const char *codec_name, size_t frames_per_packet, size_t 
         st->salt = s * 7;
         st->lead = lead_of(s);
         st->limit = total + st->lead + 2 * a.lookahead;  // (no stream ends inside the timed region: a tail batch is a shape of its own)
-        auto peek = [st, &pool]() -> std::optional<Packet> {
+        auto peek = [st, &pool, tweak]() -> std::optional<Packet> {
             if (st->cursor >= st->limit) return std::nullopt;
             Packet p = pool[(st->cursor + st->salt) % kPool];  // (the copy a parser's output costs)
+            tweak(p, st->cursor);
             p.ts = st->cursor++;
             return p;
         };
@@ -379,7 +409,7 @@ int run(const Args &a, const char *codec_name, size_t frames_per_packet, size_t 
                             if (lead && step >= first + count + st.lead) continue;  // (the warm-up runs stream s `lead` packets further)
                             const size_t i = st.pos++;
                             Packet p;
-                            if (full) p = pool[(i + st.salt) % kPool];
+                            if (full) p = pool[(i + st.salt) % kPool], tweak(p, i);
                             p.ts = i;
                             if (st.cursor <= i) st.cursor = i + 1;
                             if (batcher) {
@@ -418,6 +448,18 @@ int run(const Args &a, const char *codec_name, size_t frames_per_packet, size_t 
     size_t batches = 0, verified = 0, narrow_batches = 0, wide_batches = 0;
     for (auto &st : streams) batches += st->dec->batches_run();
     for (auto &st : streams) narrow_batches += st->dec->narrow_batches(), wide_batches += st->dec->wide_batches();
+    // --narrow 2: the rows that went up at 2, 3 and 4 bytes a word (warm-up included), and what went up per packet: the bytes of plane 0 the
+    // decoders handed over, over the packets they were of, plus the other planes and a width byte per row
+    size_t rows_sent[3] = {0, 0, 0}, plane0_bytes = 0;
+    for (auto &st : streams) {
+        const std::array<std::size_t, 3> r = st->dec->rows_sent();
+        rows_sent[0] += r[0], rows_sent[1] += r[1], rows_sent[2] += r[2];
+        plane0_bytes += st->dec->plane0_bytes();
+    }
+    if (const size_t rows = rows_sent[0] + rows_sent[1] + rows_sent[2]) {
+        const size_t nch = params<Codec>().channels;
+        bytes_in_per_packet = bytes_in_per_packet - frames_per_packet * nch * 4 + (plane0_bytes + rows / nch / 2) / (rows / nch) + nch;
+    }
     // (what went up per packet: half of the words' bytes if every batch went narrow; the counts cover the warm-up too)
     if (narrow_batches && !wide_batches) bytes_in_per_packet -= frames_per_packet * params<Codec>().channels * 2;
     for (auto &st : streams) verified += st->dec->finalize().verify_ok.value_or(false) ? 1 : 0;
@@ -431,7 +473,7 @@ int run(const Args &a, const char *codec_name, size_t frames_per_packet, size_t 
                 "\"packets_per_s\": %.1f, \"frames_per_packet\": %zu, \"host_bytes_in_per_packet\": %zu, \"host_bytes_out_per_packet\": %zu, "
                 "\"GBps_each_way\": [%.3f, %.3f], \"decoder_batches\": %zu, \"launches\": %llu, \"kernel_launches\": %llu, \"max_chains_per_launch\": %llu, "
                 "\"staging_bytes\": %llu, \"staging_grew_bytes\": %llu, \"slots_peak\": [%llu, %llu], \"lanes\": %llu, \"mutex_wait_ms\": %.3f, \"mutex_contended\": %llu, \"launch_host_ms\": %.3f, \"launch_api_ms\": %.3f, \"lane_wait_ms\": %.3f, \"group_allocs\": %llu, \"blocks\": %llu, \"flag_wait_ms\": %.3f, \"commit_to_launch_ms_per_submission\": %.3f, \"waits\": %llu, \"waits_blocked\": %llu, \"launch_to_done_ms\": %.3f, "
-                "\"failed_tickets\": %llu, \"failures\": %zu, \"checksum\": %llu, \"out_format\": \"%s\", \"flag_wait_ns\": %llu, \"verify\": %s, \"streams_verified\": %zu, \"bits\": %zu, \"narrow_batches\": %zu, \"wide_batches\": %zu}\n",
+                "\"failed_tickets\": %llu, \"failures\": %zu, \"checksum\": %llu, \"out_format\": \"%s\", \"flag_wait_ns\": %llu, \"verify\": %s, \"streams_verified\": %zu, \"bits\": %zu, \"narrow_batches\": %zu, \"wide_batches\": %zu, \"rows_sent\": [%zu, %zu, %zu], \"plane0_bytes\": %zu, \"wide_every\": %zu, \"warmup_bits\": %zu}\n",
                 codec_name, a.via_registry ? "registry" : (batcher ? "batcher" : "per-stream"), a.direct ? "true" : "false", a.in_phase ? "true" : "false", a.streams, a.lookahead, std::min(a.threads, a.streams), n, secs, n / secs, frames_per_packet,
                 bytes_in_per_packet, frames_per_packet * params<Codec>().channels * out_sample_bytes, n * bytes_in_per_packet / secs / 1e9,
                 n * frames_per_packet * params<Codec>().channels * out_sample_bytes / secs / 1e9, batches,
@@ -441,7 +483,7 @@ int run(const Args &a, const char *codec_name, size_t frames_per_packet, size_t 
                 (double)(s1.launch_host_ns - s0.launch_host_ns) / 1e6, (double)(s1.launch_api_ns - s0.launch_api_ns) / 1e6,
                 (double)(s1.lane_wait_ns - s0.lane_wait_ns) / 1e6, (unsigned long long)(s1.group_allocs - s0.group_allocs), (unsigned long long)s1.blocks, (double)(s1.flag_wait_ns - s0.flag_wait_ns) / 1e6, (double)(s1.commit_to_launch_ns - s0.commit_to_launch_ns) / 1e6 / (double)std::max<uint64_t>(1, s1.submissions - s0.submissions), (unsigned long long)(s1.waits - s0.waits), (unsigned long long)(s1.waits_blocked - s0.waits_blocked), (double)(s1.launch_to_done_ns - s0.launch_to_done_ns) / 1e6 / (double)std::max<uint64_t>(1, s1.launches_timed - s0.launches_timed),
                 (unsigned long long)(s1.failed_tickets - s0.failed_tickets), failures.load(),
-                (unsigned long long)checksum.load(), a.out_format.c_str(), (unsigned long long)(s1.flag_wait_ns - s0.flag_wait_ns), a.verify ? "true" : "false", verified, a.bits, narrow_batches, wide_batches);
+                (unsigned long long)checksum.load(), a.out_format.c_str(), (unsigned long long)(s1.flag_wait_ns - s0.flag_wait_ns), a.verify ? "true" : "false", verified, a.bits, narrow_batches, wide_batches, rows_sent[0], rows_sent[1], rows_sent[2], plane0_bytes, a.wide_every, a.warmup_bits);
     return failures.load() ? 1 : 0;
 }
 
@@ -468,13 +510,16 @@ int main(int argc, char **argv) {
         else if (k == "--out-format" && i + 1 < argc) a.out_format = argv[++i];
         else if (k == "--bits") a.bits = val();
         else if (k == "--narrow") a.narrow = (int)val();
+        else if (k == "--wide-every") a.wide_every = val();
+        else if (k == "--warmup-bits") a.warmup_bits = val();
         else {
             std::fprintf(stderr, "unknown argument %s\n", k.c_str());
             return 2;
         }
     }
-    if (!a.streams || !a.lookahead || !a.packets || !a.threads || (a.bits != 16 && a.bits != 24)) return 2;
+    if (!a.streams || !a.lookahead || !a.packets || !a.threads || (a.bits != 16 && a.bits != 24) || a.warmup_bits > 32 || a.warmup_bits == 1 || a.narrow > 2) return 2;
     g_flac_bits = a.bits;
+    g_flac_warmup_bits = a.warmup_bits;
     if (!a.warm) a.warm = 4 * a.lookahead;  // past the cold start (every stream's first batch is a launch of its own) and the pool's growth
     try {
         if (a.codec == "aac") return run<AacLc>(a, "aac", 1024, 2 * 1024 * 4 + 2);
