@@ -264,3 +264,108 @@ def floor1_case(rng):
     ys = rng.integers(0, top, size=(count, n_posts)).astype(np.uint32)
     ys[rng.random((count, n_posts)) < rng.choice([0.02, 0.3, 0.9])] = 0
     return xs, mult, n, ys
+
+
+def _floor1_where(a):
+    if type(a).__module__.split(".")[0] == "torch":
+        import torch
+        return torch, torch.where
+    return np, np.where
+
+
+def floor1_spec_model(xs, ys, mult, n, lines="dda"):
+    """Vorbis I 7.2.4 (floor 1 curve computation) in plain integers: the dB-table index of every line, uint8[n] for one row of y
+    values -- or uint8[count, n] for ys[count, n_posts]; the rows are independent, the arithmetic runs on all of them at once.
+
+    Step 1: low / high neighbours (7.2.2.2), render_point (7.2.2.4), the room / far / near rule and the step-2 flags; step 2:
+    the flagged posts in x order, the heights times the multiplier clamped to 0 .. 255, integer render_line (7.2.2.5: the
+    base / sy / ady / err recurrence, one line at a time) and the flat tail; a segment that starts at or beyond n renders nothing
+    and one that ends beyond n stops at n.  For y values beyond the floor's range (up to 511) the spec is silent: the model then
+    follows the reference decoder's i32 arithmetic (symphonia-codec-vorbis floor.rs:568-653) -- `predicted` may leave
+    0 .. range, `room` may be negative, the far / near selection and `val - lowroom + predicted` are taken as written, and only
+    the product with the multiplier is clamped.  Written from the spec and that text, not from the kernel or the C oracle.
+
+    lines="dda" (numpy only) walks render_line's recurrence; lines="closed" writes each segment as
+    y0 + sign(dy) * ((|dy| * t) // adx), the same integers without the walk, on whatever array library `ys` belongs to (numpy or
+    torch, any device): the form the device-side sweeps can afford.  The tests hold the two against each other and the oracle."""
+    xs = [int(v) for v in xs]
+    n_posts = len(xs)
+    assert n_posts >= 2 and min(xs) == 0 and len(set(xs)) == n_posts
+    xp, where = _floor1_where(ys)
+    if xp is np:
+        ys = np.asarray(ys)
+    one_row = len(ys.shape) == 1
+    y2 = (ys.astype(np.int64) if xp is np else ys.to(xp.int64)).reshape(-1, n_posts)
+    range_ = (256, 128, 86, 64)[mult - 1]
+    # ---- step 1
+    fy = [y2[:, 0], y2[:, 1]]
+    always = y2[:, 0] == y2[:, 0]
+    flag = [always, always]
+    for i in range(2, n_posts):
+        lo = max((j for j in range(i) if xs[j] < xs[i]), key=lambda j: xs[j])
+        hi = min((j for j in range(i) if xs[j] > xs[i]), key=lambda j: xs[j])
+        dy, adx = fy[hi] - fy[lo], xs[hi] - xs[lo]
+        off = (abs(dy) * (xs[i] - xs[lo])) // adx  # render_point
+        predicted = where(dy < 0, fy[lo] - off, fy[lo] + off)
+        val, highroom, lowroom = y2[:, i], range_ - predicted, predicted
+        room = 2 * where(highroom < lowroom, highroom, lowroom)
+        far = where(highroom > lowroom, val - lowroom + predicted, predicted - val + highroom - 1)
+        near = where((val & 1) == 1, predicted - (val + 1) // 2, predicted + val // 2)
+        coded = val != 0
+        fy.append(where(coded, where(val >= room, far, near), predicted))
+        flag[lo], flag[hi] = flag[lo] | coded, flag[hi] | coded
+        flag.append(coded)
+    # ---- step 2: the posts in x order (stable), heights in table units
+    order = sorted(range(n_posts), key=lambda i: xs[i])
+    sx = [xs[i] for i in order]
+    height = [(fy[i] * mult).clip(0, 255) for i in order]
+    used = [flag[i] for i in order]
+    count = y2.shape[0]
+    if lines == "closed":
+        t = (np.arange(n, dtype=np.int64) if xp is np else xp.arange(n, dtype=xp.int64, device=y2.device))[None, :]
+        curve = (np.zeros((count, n), np.int64) if xp is np else xp.zeros((count, n), dtype=xp.int64, device=y2.device))
+        lx, ly = 0 * y2[:, 0], height[0]
+        for k in range(1, n_posts):
+            end = min(sx[k], n)
+            dy, adx = height[k] - ly, sx[k] - lx
+            adx = where(adx > 0, adx, 1 + 0 * adx)  # (rows that do not use this post)
+            tt = t[:, :end] - lx[:, None]
+            y = ly[:, None] + where(dy < 0, -1 + 0 * dy, 1 + 0 * dy)[:, None] * ((abs(dy)[:, None] * tt) // adx[:, None])
+            curve[:, :end] = where(used[k][:, None] & (tt >= 0), y, curve[:, :end])
+            lx, ly = where(used[k], sx[k] + 0 * lx, lx), where(used[k], height[k], ly)
+        curve = where(t >= lx[:, None], ly[:, None] + 0 * curve, curve)  # flat tail (hx < n)
+        out = curve.astype(np.uint8) if xp is np else curve.to(xp.uint8)
+        return out[0] if one_row else out
+    assert lines == "dda" and xp is np
+    # per x-sorted position: the next flagged post to its right (x, height), -1 if there is none (then the flat tail follows)
+    next_x, next_y = [None] * n_posts, [None] * n_posts
+    nx, ny = np.full(count, -1, np.int64), np.zeros(count, np.int64)
+    for k in range(n_posts - 1, -1, -1):
+        next_x[k], next_y[k] = nx, ny
+        nx, ny = np.where(used[k], sx[k], nx), np.where(used[k], height[k], ny)
+    starts = {sx[k]: k for k in range(1, n_posts)}
+    curve = np.zeros((count, n), np.int64)
+    y = err = adx = ady = base = sy = None
+    for x in range(n):
+        k = 0 if x == 0 else starts.get(x)
+        if x:
+            err = err + ady
+            over = err >= adx
+            err = np.where(over, err - adx, err)
+            y = y + np.where(over, sy, base)
+        if k is not None:  # render_line(lx, ly, hx, hy) begins here for the rows that use this post (all of them at x = 0)
+            new = np.ones(count, bool) if x == 0 else used[k]
+            hx = np.where(next_x[k] >= 0, next_x[k], n)
+            hy = np.where(next_x[k] >= 0, next_y[k], height[k])
+            dy, dx = hy - height[k], hx - x
+            b = np.where(dy < 0, -1, 1) * (np.abs(dy) // dx)  # dy / adx, truncating
+            s, a = np.where(dy < 0, b - 1, b + 1), np.abs(dy) - np.abs(b) * dx
+            if x == 0:
+                y, err, adx, ady, base, sy = height[0], np.zeros(count, np.int64), dx, a, b, s
+            else:
+                y, err = np.where(new, height[k], y), np.where(new, 0, err)
+                adx, ady, base, sy = np.where(new, dx, adx), np.where(new, a, ady), np.where(new, b, base), np.where(new, s, sy)
+        curve[:, x] = y
+    assert curve.min() >= 0 and curve.max() <= 255
+    out = curve.astype(np.uint8)
+    return out[0] if one_row else out

@@ -245,3 +245,11 @@ def test_fuzz_vorbis_floor1(ctx, it):
     d_res = dev(res)
     v.floor1(xs, mult, dev(ys), n, d_res, len(ys), residue=d_res)
     assert bit_equal(host(d_res), curve * res), (n, len(xs), mult, len(ys))
+
+
+@pytest.mark.parametrize("it", range(4 * ITERS))
+def test_fuzz_vorbis_floor1_bytes(ctx, it):
+    """the same distribution through the byte kernels (what symaccel_vorbis_decode and the batcher run): aligned and 4-, 8-, 12-byte-offset
+    block starts, one call and two jobs of different n in one launch (test_vorbis_floor_y.check_floor1_bytes_fuzz)"""
+    from test_vorbis_floor_y import check_floor1_bytes_fuzz
+    check_floor1_bytes_fuzz(ctx, dev, host, 7600 + it)

@@ -8,7 +8,7 @@ import pytest
 
 import oracle
 from helpers import (aac_sequence_chain, imdct_analytical, mdct_forward, imdct36_analytical,
-                     imdct12_analytical)
+                     imdct12_analytical, floor1_spec_model)
 
 # ----------------------------------------------------------------------------- AAC
 
@@ -356,57 +356,7 @@ def test_vorbis_floor1_render_against_spec_model():
         ys = rng.integers(0, rng_range, size=n_posts)
         ys[rng.random(n_posts) < 0.3] = 0
         got = oracle.vorbis_floor1(xs, ys, mult, n)
-        # spec model
-        def low_high(i):
-            lo = max((j for j in range(i) if xs[j] < xs[i]), key=lambda j: xs[j])
-            hi = min((j for j in range(i) if xs[j] > xs[i]), key=lambda j: xs[j])
-            return lo, hi
-        def render_point(x0, y0, x1, y1, x):
-            dy, adx = y1 - y0, x1 - x0
-            off = abs(dy) * (x - x0) // adx
-            return y0 - off if dy < 0 else y0 + off
-        fy, fl = [int(ys[0]), int(ys[1])], [True, True]
-        for i in range(2, n_posts):
-            lo, hi = low_high(i)
-            pred = render_point(xs[lo], fy[lo], xs[hi], fy[hi], xs[i])
-            val, hr, lr = int(ys[i]), rng_range - pred, pred
-            room = 2 * min(hr, lr)
-            if val:
-                fl[lo] = fl[hi] = True
-                fl.append(True)
-                if val >= room:
-                    fy.append(val - lr + pred if hr > lr else pred - val + hr - 1)
-                else:
-                    fy.append(pred - (val + 1) // 2 if val & 1 else pred + val // 2)
-            else:
-                fl.append(False)
-                fy.append(pred)
-        order = sorted(range(n_posts), key=lambda i: xs[i])
-        curve = np.zeros(n, dtype=np.int64)
-        lx, ly = 0, min(max(fy[order[0]] * mult, 0), 255)
-        hx = hy = 0
-        for i in order[1:]:
-            if fl[i]:
-                hy, hx = min(max(fy[i] * mult, 0), 255), xs[i]
-                # spec render_line (integer Bresenham)
-                dy, adx = hy - ly, hx - lx
-                base = abs(dy) // adx * (1 if dy >= 0 else -1)
-                sy = base - 1 if dy < 0 else base + 1
-                ady = abs(dy) - abs(base) * adx
-                y, err = ly, 0
-                if lx < n:
-                    curve[lx] = y
-                for x in range(lx + 1, min(hx, n)):
-                    err += ady
-                    if err >= adx:
-                        err -= adx
-                        y += sy
-                    else:
-                        y += base
-                    curve[x] = y
-                lx, ly = hx, hy
-        if hx < n:
-            curve[hx:] = hy
+        curve = floor1_spec_model(xs, ys, mult, n)
         assert np.array_equal(got, table[curve]), trial
 
 

@@ -101,6 +101,68 @@ def test_emu_floor1_y_jobs(emu_ctx):
     check_floor1_y_jobs(emu_ctx, lambda a: a, lambda a: a)
 
 
+def check_floor1_bytes_fuzz(ctx, to_dev, to_host, seed):
+    """helpers.floor1_case -- posts beyond the block, neighbour spans above 4096, runs of adjacent x, y up to 511, a last workgroup of
+    two blocks -- through the BYTE kernels: one call with block starts that are 16-byte aligned or 4, 8, 12 bytes off (by seed), then
+    two draws of different n as two jobs into one plane.  == the oracle's curve through the dB table; every other byte stays poison."""
+    from helpers import floor1_case
+    rng = np.random.default_rng(seed)
+    v = VorbisDsp(ctx, 8, 11)
+    db = db_table()
+    draws = [floor1_case(rng)]
+    while len(draws) < 2:
+        d = floor1_case(rng)
+        if d[2] != draws[0][2]:
+            draws.append(d)
+    wants = [np.stack([oracle.vorbis_floor1(xs, y, mult, n) for y in ys]) for xs, mult, n, ys in draws]
+
+    def verify(got, placed, what):
+        seen = np.zeros(got.size, bool)
+        for (xs, mult, n, ys), want, offs in placed:
+            for b in range(len(ys)):
+                assert bit_equal(db[got[offs[b]:offs[b] + n]], want[b]), (seed, what, n, len(xs), mult, b)
+                seen[offs[b]:offs[b] + n] = True
+        assert np.all(got[~seen] == 0x5A), (seed, what)
+
+    def place(draw, base, shift):
+        n, count = draw[2], len(draw[3])
+        offs = rng.permutation(count).astype(np.uint32) * np.uint32(n + 16) + np.uint32(base + shift)
+        return offs, base + count * (n + 16) + 16
+
+    shift = (0, 4, 8, 12)[seed % 4]
+    offs, size = place(draws[0], 16, shift)
+    plane = to_dev(np.full(size + 64, 0x5A, np.uint8))
+    xs, mult, n, ys = draws[0]
+    v.floor1(xs, mult, to_dev(ys), n, None, len(ys), y_plane=plane, line_offsets=to_dev(offs))
+    verify(to_host(plane), [(draws[0], wants[0], offs)], "one call")
+    # two jobs, one launch: the second job's blocks start at another offset from the boundary
+    offs0, base = place(draws[0], 16, shift)
+    offs1, size = place(draws[1], base, (shift + 4 * (1 + seed // 4 % 3)) % 16)
+    plane = to_dev(np.full(size + 64, 0x5A, np.uint8))
+    v.floor1_y_jobs([(d[0], d[1], to_dev(d[3]), d[2], to_dev(o), len(d[3])) for d, o in zip(draws, (offs0, offs1))], plane)
+    verify(to_host(plane), [(draws[0], wants[0], offs0), (draws[1], wants[1], offs1)], "two jobs")
+
+
+EMU_FUZZ_SEEDS = (7602, 7603, 7604, 7605, 7608, 7613, 7617, 7622)
+
+
+@pytest.mark.parametrize("seed", EMU_FUZZ_SEEDS)
+def test_emu_floor1_bytes_fuzz(emu_ctx, seed):
+    check_floor1_bytes_fuzz(emu_ctx, lambda a: a, lambda a: a, seed)
+
+
+def test_spec_model_agrees_with_the_oracle_on_the_fuzz_draws():
+    """CPU only: on the draws of the seeds above and of test_gpu_fuzz.py's default 24 (both draws of each), the independent model of
+    Vorbis I 7.2.4 (helpers.floor1_spec_model) through the dB table == the oracle that judges the kernels, bit for bit"""
+    from helpers import floor1_case, floor1_spec_model
+    db = db_table()
+    for seed in sorted(set(EMU_FUZZ_SEEDS) | set(range(7600, 7624))):
+        rng = np.random.default_rng(seed)
+        for _ in range(2):
+            xs, mult, n, ys = floor1_case(rng)
+            assert bit_equal(db[floor1_spec_model(xs, ys, mult, n)], np.stack([oracle.vorbis_floor1(xs, y, mult, n) for y in ys])), seed
+
+
 def fy_case(rng, bs0e, bs1e, nch, nb):
     from test_emu_codecs import vorbis_case
     flags, prev, residue, overlap, pcm_stride = vorbis_case(rng, bs0e, bs1e, nch, nb)
